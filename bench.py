@@ -21,7 +21,16 @@ line: its rank count and whether its sums equal the host group's).  The GPU
 process never imports torch (torch ships its own HIP runtime with the same
 SONAME).
 
-Adds to the JSON line:
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times
+the K steps and prints the line: the headline figures, the work counters, the
+per-rank host budget and the timed region's own roofline figures (its sampled
+HIP events and the committed PMC record; nothing that takes a run of its own).
+`--dump-outputs DIR` also writes what the timed path handed its caller in the
+last step (dump_outputs below).  Everything else is measured under `--full`.
+
+`--full` adds to the JSON line (each can be switched off by its --no-* flag):
+  lockstep      one lockstep batch of G games beside the streamed headline
+  roofline.isolated  the forward launch alone on the GPU
   roofline      the fused forward kernel (dominant) vs the 2.5 PF dense bf16
                 MFMA peak.  achieved/frac = job level: the algorithmic FLOPs of
                 every leaf evaluated in the timed region over its wall time (the
@@ -80,24 +89,31 @@ def parse():
     ap.add_argument("--sims", type=int, default=800, help="MCTS simulations per move")
     ap.add_argument("--blocks", type=int, default=6)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: the one-step lockstep "
+                         "figure, the isolated forward, the rules kernels, the chess window and the CPU baselines "
+                         "(vs_baseline); each has its own --no-* switch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the samples the timed path emitted for (a fixed, seeded sample of) its last step's "
+                         "games, and the timed region's work counters, as DIR/<name>.npy (rank 0)")
     ap.add_argument("--lockstep", action="store_true",
                     help="one lockstep batch of G games per step (every game starts together; the batch thins out "
                          "as games end) instead of the default stream: the steps' K x G games played through G tree "
                          "slots, a slot taking the next game when its game ends (spai_selfplay_stream)")
     ap.add_argument("--stream", action="store_true", help=argparse.SUPPRESS)   # the default; kept for old scripts
     ap.add_argument("--no-lockstep-ref", action="store_true",
-                    help="skip the one-step lockstep figure reported beside the streamed headline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: skip the one-step lockstep figure reported beside the streamed headline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (vs_baseline)")
     ap.add_argument("--cpu-games", type=int, default=100,
                     help="games the CPU baseline plays to completion inside this run: the reference worker's batch "
                          "(learner_concurrent.rs:50-59, num_batched_self_play_games = 100), ~2 min on the GPU box's host")
     ap.add_argument("--cpu-timeout", type=float, default=360.0)
     ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--no-rules-bench", action="store_true", help="skip the batched rules-kernel timing (HBM GB/s)")
-    ap.add_argument("--no-chess", action="store_true", help="skip the chess window (config 4, 2 moves)")
+    ap.add_argument("--no-rules-bench", action="store_true", help="--full: skip the batched rules-kernel timing (HBM GB/s)")
+    ap.add_argument("--no-chess", action="store_true", help="--full: skip the chess window (config 4, 2 moves)")
     ap.add_argument("--chess-moves", type=int, default=2)
     ap.add_argument("--no-timing", action="store_true", help="no per-kernel HIP events (A/B of their cost)")
-    ap.add_argument("--no-isolated", action="store_true", help="skip the isolated-forward measurement")
+    ap.add_argument("--no-isolated", action="store_true", help="--full: skip the isolated-forward measurement")
     ap.add_argument("--traffic-json", default=os.path.join(REPO, "profiles", "r05", "final", "forward_traffic.json"),
                     help="PMC summary (scripts/gpu_traffic.sh) of this bench command: HBM bytes per k_forward launch")
     ap.add_argument("--pmc-json", default=os.path.join(REPO, "profiles", "r06", "final_s3", "forward_pmc.json"),
@@ -419,6 +435,40 @@ def stream_base(first, k, world, rank, G):
     return (first * world + rank * k) * G
 
 
+DUMP_GAMES = 512   # games of the last step kept for --dump-outputs (all of them when the step has fewer)
+
+
+def dump_ids(first, n, seed):
+    """the game ids --dump-outputs keeps: a fixed sample (seeded, so the same for
+    every run with the same arguments) of DUMP_GAMES of the last step's n games,
+    ids [first, first + n)"""
+    import numpy as np
+    if n <= DUMP_GAMES:
+        return frozenset(range(first, first + n))
+    pick = np.random.default_rng(seed).choice(n, DUMP_GAMES, replace=False)
+    return frozenset(int(first + i) for i in pick)
+
+
+def dump_outputs(path, games, counters):
+    """what a caller of the timed path received, as float32 / float64 .npy files:
+    the samples of the kept games in game-id order (a game's draws are keyed by its
+    id, so the arrays do not depend on the order the games finished in), at most
+    DUMP_GAMES x 42 positions x 135 floats = 11.6 MB, and the timed region's work
+    counters.  game_id[g] and positions[g] give game g's id and its number of
+    samples; enc / policy / value / moves hold the games' samples back to back."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    games = sorted(games, key=lambda g: g["game"])
+    cat = lambda k, shape, dt: (np.concatenate([g[k] for g in games]) if games else np.zeros(shape)).astype(dt)
+    out = {"game_id": np.array([g["game"] for g in games], np.float64),
+           "positions": np.array([len(g["value"]) for g in games], np.float64),
+           "enc": cat("enc", (0, 126), np.float32), "policy": cat("policy", (0, 7), np.float32),
+           "value": cat("value", (0,), np.float32), "moves": cat("moves", (0,), np.float32),
+           "counters": np.array([counters[k] for k in ("sims", "evals", "games", "positions")], np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     args = parse()
     if args.cpu_baseline_only:
@@ -448,18 +498,27 @@ def main():
     comm, comm_note = rccl_comm(dist, spai)
     G = args.games
 
+    streaming = not args.lockstep
+    # --dump-outputs: the sink keeps the samples of these games of the last timed step (rank 0)
+    keep, kept = None, []
+    if args.dump_outputs and dist.rank == 0 and args.steps > 0:
+        # rank 0's last G timed ids: the tail of its stream, or its last lockstep batch
+        last = (args.steps - 1) * G * (1 if streaming else dist.world)
+        keep = dump_ids(last, G, args.seed).__contains__
+
     def step(i):
         base = (i * dist.world + dist.rank) * G
-        _, st = eng.self_play(G, game_id_base=base, collect=False)
+        gs, st = eng.self_play(G, game_id_base=base, collect=keep if keep and i >= 0 else False)
+        kept.extend(gs)
         return st
 
     def stream(first, k):
         """k steps' worth of games through G tree slots (stream_base)"""
         base = stream_base(first, k, dist.world, dist.rank, G)
-        _, st = eng.self_play(k * G, game_id_base=base, collect=False, window=G)
+        gs, st = eng.self_play(k * G, game_id_base=base, collect=keep if keep and first >= 0 else False, window=G)
+        kept.extend(gs)
         return st
 
-    streaming = not args.lockstep
     if streaming:
         if args.warmup:
             stream(-args.warmup, args.warmup)
@@ -489,6 +548,8 @@ def main():
     dist.barrier()
     dt = time.perf_counter() - t0
     timing = eng.timing()
+    if args.dump_outputs and dist.rank == 0:
+        dump_outputs(args.dump_outputs, kept, tot)
     # host CPU time of this rank's process (every thread: the self-play host loop, the HIP
     # runtime's) over the timed region: the host-core budget per GPU
     cpu_s = (ru1.ru_utime - ru0.ru_utime) + (ru1.ru_stime - ru0.ru_stime)
@@ -616,7 +677,7 @@ def main():
     }
     # the lockstep schedule beside the streamed headline: one step of G games started
     # together (game ids after the timed region's), rank 0 of a 1-rank run
-    if streaming and not args.no_lockstep_ref:   # every rank, its own game ids after the timed region's
+    if args.full and streaming and not args.no_lockstep_ref:   # every rank, its own game ids after the timed region's
         eng.set_timing(False)
         eng.sync()
         dist.barrier()
@@ -635,7 +696,7 @@ def main():
     # the same forward launch ALONE on the GPU (spai_net_bench, HIP events, random reachable
     # positions) at the timed region's mean leaves per launch, at one chain's (x2) and at the
     # full-batch sizes: the isolated-kernel roofline beside the shared-CU per-launch figure above
-    if dist.rank == 0 and not args.no_isolated:
+    if args.full and dist.rank == 0 and not args.no_isolated:
         iso = {}
         mean_leaves = int(round(ev["items"] / max(1, ev["launches"])))
         net.bench(G, iters=1500)   # ~0.2 s of launches first: time at the clock the GPU holds under load
@@ -656,16 +717,16 @@ def main():
                                                "group size the timed region's two chains use (spai_net_bench_conc); "
                                                "the timed region's per-launch figure shares the CUs with the other "
                                                "search chain")
-    if not args.no_rules_bench and dist.rank == 0:
+    if args.full and not args.no_rules_bench and dist.rank == 0:
         result["rules_kernels"] = rules_bench(eng)
     net.close()
     eng.close()
-    if not args.no_chess and dist.rank == 0:
+    if args.full and not args.no_chess and dist.rank == 0:
         try:
             result["chess"] = chess_window(args, dist.local, dist.world)
         except Exception as ex:   # the window must never sink the headline number
             result["chess"] = {"error": repr(ex)[:300]}
-    if dist.rank == 0 and dist.world == 1 and not args.no_cpu_baseline:
+    if args.full and dist.rank == 0 and dist.world == 1 and not args.no_cpu_baseline:
         cb = run_cpu_baseline(args)
         result["cpu_baseline"] = cb
         # BASELINE.md publishes no number for this metric: the ratio is against the CPU

@@ -30,7 +30,7 @@ if has tests; then
   rc=$?; tail -3 $O/pytest_gpu.log; echo "pytest rc=$rc"; [ $rc -eq 0 ] || exit $rc
 fi
 if has bench; then
-  timeout -k 10 900 python bench.py ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err
+  timeout -k 10 900 python bench.py --full ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err
   rc=$?; cat $O/bench.json; tail -3 $O/bench.err; echo "bench rc=$rc"; [ $rc -eq 0 ] || exit $rc
 fi
 if has trace; then

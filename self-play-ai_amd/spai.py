@@ -412,11 +412,13 @@ class Engine:
     def self_play(self, n_games, game_id_base=0, collect=True, window=None):
         """SelfPlayWorker::self_play over n_games games (spai_selfplay_run); window:
         play them through that many tree slots, refilled as games end
-        (spai_selfplay_stream)"""
+        (spai_selfplay_stream); collect: keep every game's samples, none, or (a
+        callable) those of the games whose id it accepts"""
         games = []
+        some = callable(collect)
 
         def sink(user, gid, n, enc, pol, val, moves):
-            if collect:
+            if collect(gid) if some else collect:
                 games.append(dict(game=gid,
                                   enc=np.ctypeslib.as_array(enc, (n, 126)).copy(),
                                   policy=np.ctypeslib.as_array(pol, (n, 7)).copy(),

@@ -739,7 +739,11 @@ def mcts_main():
 
 
 def learner_main():
-    np.savez_compressed(os.path.join(HERE, "learner_c4_1x64.npz"), **learner_golden())
+    # two files, each under the 1 MiB limit for a committed file: the parameters after the
+    # third step apart from the batches, losses and the first step's gradients / parameters
+    g = learner_golden()
+    np.savez_compressed(os.path.join(HERE, "learner_c4_1x64_step3.npz"), params3=g.pop("params3"))
+    np.savez_compressed(os.path.join(HERE, "learner_c4_1x64.npz"), **g)
 
 
 if __name__ == "__main__":

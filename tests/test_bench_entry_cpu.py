@@ -126,6 +126,53 @@ def test_schedule_flags_parse(monkeypatch):
         assert a.lockstep is lock and not a.no_lockstep_ref
 
 
+def test_full_and_dump_flags_parse(monkeypatch):
+    """a plain run measures the headline only: --full (off by default) turns the other
+    measurements on, their --no-* switches still parse, --dump-outputs takes a directory"""
+    sys.path.insert(0, REPO)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-chess", "--no-cpu-baseline", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.no_chess and a.no_cpu_baseline and a.dump_outputs == "d"
+
+
+def test_dump_sample_and_files(tmp_path):
+    """--dump-outputs: the kept ids are a fixed function of the arguments (all of a small
+    step, a seeded DUMP_GAMES-subset of a large one, inside the step's id range), and the
+    files hold the kept games in id order whatever order they finished in, as float32 /
+    float64"""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    assert bench.dump_ids(192, 96, 0) == frozenset(range(192, 288))
+    big = bench.dump_ids(8192, 4096, 0)
+    assert big == bench.dump_ids(8192, 4096, 0) and len(big) == bench.DUMP_GAMES
+    assert min(big) >= 8192 and max(big) < 8192 + 4096 and big != bench.dump_ids(8192, 4096, 1)
+    # the whole dump stays far below 64 MB at the longest possible games
+    assert bench.DUMP_GAMES * 42 * (126 + 7 + 1 + 1) * 4 < 64e6
+
+    def game(gid, n):
+        return dict(game=gid, enc=np.full((n, 126), gid, np.float32), policy=np.full((n, 7), gid, np.float32),
+                    value=np.full(n, gid, np.float32), moves=np.full(n, gid, np.int32))
+
+    counters = dict(sims=5.0, evals=4.0, games=2.0, positions=5.0, moves=3.0)
+    bench.dump_outputs(str(tmp_path / "a"), [game(7, 3), game(5, 2)], counters)
+    bench.dump_outputs(str(tmp_path / "b"), [game(5, 2), game(7, 3)], counters)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(n + ".npy" for n in ("game_id", "positions", "enc", "policy", "value", "moves", "counters"))
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    assert list(np.load(tmp_path / "a" / "game_id.npy")) == [5, 7]
+    assert list(np.load(tmp_path / "a" / "positions.npy")) == [2, 3]
+    assert list(np.load(tmp_path / "a" / "value.npy")) == [5, 5, 7, 7, 7]
+    assert np.load(tmp_path / "a" / "enc.npy").shape == (5, 126)
+    assert list(np.load(tmp_path / "a" / "counters.npy")) == [5, 4, 2, 5]
+
+
 @pytest.mark.parametrize("world", [1, 2, 8])
 def test_stream_game_ids_partition(world):
     """the streamed bench's game ids: the ranks' ranges tile the job's range with no

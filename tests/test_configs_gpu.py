@@ -206,3 +206,65 @@ def test_bench_gpus_flag_spawns_ranks():
             assert abs(r["host_cpu_share"] - r["host_cpu_s"] / r["wall_s"]) < 1e-9
         assert line["host"]["cpu_share_per_rank_max"] == max(r["host_cpu_share"] for r in pr)
         assert line["schedule"] == "streamed"
+
+
+def test_bench_plain_full_and_dump(tmp_path):
+    """a plain `bench.py --gpus 1 --steps K --warmup W` times its K steps and nothing
+    else: no lockstep / isolated / rules / chess / CPU figures, vs_baseline null; --full
+    brings them back (the slow ones switched off here).  --dump-outputs writes the
+    samples of the last step's games: identical from run to run, the same games under
+    both schedules (a game's draws are keyed by its id), and equal to what
+    Engine.self_play hands a caller for those ids"""
+    import json
+    import subprocess
+    import sys
+    from conftest import REPO
+    import spai
+    G, sims, K = 96, 32, 2
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+
+    def run(extra):
+        p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--games", str(G), "--sims",
+                            str(sims), "--steps", str(K), "--warmup", "1"] + extra, env=env, capture_output=True,
+                           text=True, timeout=240)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = p.stdout.splitlines()
+        assert len(lines) == 1 and lines[0].startswith("{"), p.stdout[-2000:]
+        return json.loads(lines[0])
+
+    def load(d):
+        return {n[:-4]: np.load(os.path.join(d, n)) for n in sorted(os.listdir(d))}
+
+    moved = ("lockstep", "rules_kernels", "chess", "cpu_baseline")
+    a = run(["--dump-outputs", str(tmp_path / "a")])
+    assert not any(k in a for k in moved) and "isolated" not in a["roofline"] and a["vs_baseline"] is None
+    assert a["steps"] == K and a["work"]["games"] == K * G and a["ms_per_step"] > 0
+    assert a["unit"] == "sims/s" and a["higher_is_better"] is True and a["dtype"] == "bf16"
+    assert abs(a["value"] - a["work"]["sims"] / (K * a["ms_per_step"] * 1e-3)) <= 1e-6 * a["value"]
+    b = run(["--full", "--no-cpu-baseline", "--no-chess", "--lockstep", "--dump-outputs", str(tmp_path / "b")])
+    assert "rules_kernels" in b and "isolated" in b["roofline"] and "chess" not in b and "cpu_baseline" not in b
+    c = run(["--full", "--no-cpu-baseline", "--no-chess", "--no-isolated", "--no-rules-bench",
+             "--dump-outputs", str(tmp_path / "c")])
+    assert c["lockstep"]["steps"] == 1 and "rules_kernels" not in c
+    da, db, dc = load(tmp_path / "a"), load(tmp_path / "b"), load(tmp_path / "c")
+    assert sorted(da) == sorted(("game_id", "positions", "enc", "policy", "value", "moves", "counters"))
+    for n in da:
+        assert da[n].dtype in (np.float32, np.float64)
+        assert np.array_equal(da[n], dc[n]), n                       # run to run
+        assert np.array_equal(da[n], db[n]), n                       # streamed vs lockstep: the same games
+    assert list(da["game_id"]) == list(range((K - 1) * G, K * G))    # the last step's ids
+    assert list(da["counters"]) == [a["work"][k] for k in ("sims", "evals", "games", "positions")]
+    # what a caller of the timed path receives for those games
+    eng = spai.Engine(num_searches=sims, max_trees=G, eval_kind=spai.EVAL_NET, seed=0)
+    net = spai.Net(eng, 6, spai.init_params(6, 64, seed=0))
+    eng.set_net(net)
+    games, _ = eng.self_play(G, game_id_base=(K - 1) * G)
+    net.close()
+    eng.close()
+    games.sort(key=lambda g: g["game"])
+    assert [g["game"] for g in games] == list(da["game_id"])
+    assert [len(g["value"]) for g in games] == list(da["positions"])
+    for n in ("enc", "policy", "value", "moves"):
+        assert np.array_equal(np.concatenate([g[n] for g in games]).astype(np.float32), da[n]), n
