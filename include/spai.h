@@ -592,6 +592,34 @@ int spai_ttt_selfplay_run(spai_ttt *e, uint32_t n_games, uint64_t game_id_base, 
 /* the same games through `window` tree slots (spai_selfplay_stream's contract) */
 int spai_ttt_selfplay_stream(spai_ttt *e, uint32_t n_games, uint32_t window, uint64_t game_id_base,
                              spai_sample_sink sink, void *user, spai_selfplay_stats *stats);
+/* weight refresh of a self-play net in place (the fold + transpose of
+ * spai_ttt_net_create into the same allocations): forward afterwards is
+ * bit-identical to a net freshly created from the same parameters */
+int spai_ttt_net_set_params(spai_ttt_net *net, const float *params, size_t n_params);
+
+/* Device train step of the TicTacToe net (model/tictactoe.rs:50-81 under
+ * model/mod.rs:128-141) in fp32, on the engine's device and stream: the step of
+ * spai_learner_* on a 3x3 board with a 9-way policy head.  Parameters are the
+ * flat vector of spai_ttt_net_num_params / spai_ttt_net_init_params (BN running
+ * statistics included).  Deterministic: the same parameters and batches give
+ * bit-identical losses, gradients and parameters. */
+typedef struct spai_ttt_learner spai_ttt_learner;
+int spai_ttt_learner_create(spai_ttt *e, int blocks, const float *params, size_t n_params,
+                            const spai_adam_config *cfg /* NULL = defaults */, spai_ttt_learner **out);
+int spai_ttt_learner_destroy(spai_ttt_learner *l);
+/* states [n][27] (spai_ttt_encode layout), policies [n][9], values [n]; loss[3] = total, policy, value (may be NULL) */
+int spai_ttt_learner_train_batch(spai_ttt_learner *l, uint32_t n, const float *states, const float *policies,
+                                 const float *values, float *loss);
+/* Model::train: fresh Adam, one permutation (choose_multiple(n, n, seed, 0x7EA1B), as spai_learner_train),
+ * epochs x ceil(n/batch) steps, short last batch */
+int spai_ttt_learner_train(spai_ttt_learner *l, uint32_t n, const float *states, const float *policies,
+                           const float *values, uint32_t epochs, uint32_t batch, uint64_t seed, float *loss);
+int spai_ttt_learner_params(spai_ttt_learner *l, float *params, size_t n_params);
+int spai_ttt_learner_grads(spai_ttt_learner *l, float *grads, size_t n_params);
+/* the last train step's post-ReLU activations of conv `layer` (stem, the 2*blocks
+ * residual convs, policy conv, value conv), [B][co][3][3] */
+int spai_ttt_learner_activation(spai_ttt_learner *l, int layer, float *out, size_t n);
+int spai_ttt_learner_last_batch(spai_ttt_learner *l, uint32_t *n);
 
 #ifdef __cplusplus
 }

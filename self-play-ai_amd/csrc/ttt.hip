@@ -19,21 +19,14 @@
 
 #include "philox.h"
 #include "spai_internal.h"
+#include "ttt_engine.h"
 
 namespace spai {
 namespace ttt {
 
-constexpr int kCells = 9;
 constexpr uint32_t kFull = 0x1FF;
 constexpr uint32_t kNoChildren = 0xFFFFFFFFu;
-constexpr int kHid = 64;
-constexpr int kMaxBlocks = 16;
 constexpr uint32_t kErrNan = 1, kErrCap = 2;
-
-struct State {
-    uint16_t x, o;
-    uint8_t n, status;
-};
 
 SPAI_HD bool x_to_move(uint8_t n) { return (n & 1u) == 0; }
 
@@ -419,33 +412,6 @@ __global__ void k_tslots(State *g, uint32_t first, uint32_t n, int op, const int
 }
 
 // ---------------------------------------------------------------- engine
-struct Engine {
-    int device = 0;
-    spai_config cfg{};
-    hipStream_t stream = nullptr;
-    DevBuf<State> slots;
-    uint32_t n_slots = 0;
-    DevBuf<int32_t> si;
-    DevBuf<uint32_t> su;
-    DevBuf<float> sf, sf2;
-    // trees
-    uint32_t n_trees = 0, cap = 0;
-    DevBuf<uint4> nodes;
-    DevBuf<uint32_t> root, next_free, path, depth, active, counts, err, stats, pick;
-    DevBuf<State> root_state, leaf, adv;
-    DevBuf<uint32_t> btree;
-    DevBuf<float> bx, blogits, bvalue;
-    struct Net *net = nullptr;
-};
-
-struct Net {
-    Engine *eng = nullptr;
-    int blocks = 0;
-    DevBuf<float> wt, b, pl_w, pl_b, vl_w, vl_b;
-    DevBuf<float> io_x, io_l, io_v;
-    uint32_t io_cap = 0;
-};
-
 namespace {
 TV view(Engine *e) {
     return TV{e->nodes.p, e->root.p, e->root_state.p, e->next_free.p, e->path.p, e->depth.p, e->leaf.p, e->cap};
@@ -453,12 +419,6 @@ TV view(Engine *e) {
 BV bview(Engine *e) { return BV{e->btree.p, e->bx.p, e->blogits.p, e->bvalue.p}; }
 NetW wview(const Net *n) {
     return NetW{n->wt.p, n->b.p, n->pl_w.p, n->pl_b.p, n->vl_w.p, n->vl_b.p, n->blocks};
-}
-
-size_t num_params(int blocks) {
-    auto conv = [](size_t ci, size_t co) { return co * ci * 9 + co + 4 * co; };
-    return conv(3, kHid) + (size_t)blocks * 2 * conv(kHid, kHid) + conv(kHid, 32) + 9 * 288 + 9 + conv(kHid, 3) +
-           27 + 1;
 }
 
 float philox_unit(uint64_t seed, uint32_t tensor, uint64_t idx) {
@@ -551,9 +511,6 @@ void visit_policy(const State &root, const uint32_t *st, float *pol, uint32_t *i
 
 }  // namespace ttt
 }  // namespace spai
-
-struct spai_ttt : spai::ttt::Engine {};
-struct spai_ttt_net : spai::ttt::Net {};
 
 using namespace spai;
 using namespace spai::ttt;
