@@ -205,11 +205,40 @@ int spai_selfplay_run(spai_engine *eng, uint32_t n_games, uint64_t game_id_base,
 int spai_selfplay_stream(spai_engine *eng, uint32_t n_games, uint32_t window, uint64_t game_id_base,
                          spai_sample_sink sink, void *user, spai_selfplay_stats *stats);
 
+/* ------------------------------------------------------------------ evaluation cache
+ * With cfg.eval == SPAI_EVAL_NET the search keeps a device-resident table from
+ * the full leaf position to the net's masked priors and value, so a position
+ * the net has already seen under the current weights (other games of the call,
+ * transpositions inside a tree) is served from the table instead of going
+ * through the forward again.  A hit returns the very bytes a forward wrote for
+ * that position, so no result depends on the cache, its size or its state.
+ * It is cleared by spai_engine_set_net (new weights) and, between search
+ * calls, when it is more than 3/4 full.  Default capacity: 16384 entries per
+ * tree slot of cfg.max_trees (64 B each, at most 4 GiB); the environment
+ * variable SPAI_EVAL_CACHE=<entries> overrides the default (0: off).
+ * spai_selfplay_stats.evals counts served leaves (hits included);
+ * spai_engine_timing_items counts the leaves the forward launches ran. */
+/* entries: capacity (rounded down to a power-of-two number of 8-entry buckets, at
+ * least one bucket); 0 turns the cache off.  Takes effect at the next search call
+ * and overrides SPAI_EVAL_CACHE. */
+int spai_eval_cache_set_capacity(spai_engine *eng, uint64_t entries);
+typedef struct spai_eval_cache_stats {
+    double lookups;     /* live leaves looked up (= evals while the cache is on) */
+    double hits;        /* of them served from the table */
+    double inserts;     /* entries written */
+    double dropped;     /* inserts given up: the position's bucket was full */
+    double clears;      /* times the table was emptied (set_net, fill threshold, resize) */
+    double capacity;    /* entries of the table now (0: off) */
+} spai_eval_cache_stats;
+/* totals since the engine was created; waits for the engine's stream */
+int spai_eval_cache_get_stats(spai_engine *eng, spai_eval_cache_stats *out);
+
 /* ------------------------------------------------------------------ profiling
  * Per-kernel average device time of the last spai_selfplay_run / spai_search
  * call, measured with HIP events on each search chain's stream when enabled.
- * enabled = 1 samples every 4th search iteration; enabled = k > 1 every k-th
- * (each sampled iteration adds six event records per chain). */
+ * enabled = 1 samples every 4th search iteration; enabled = k > 1 every k-th;
+ * enabled < 0 every iteration (each sampled iteration adds six event records per
+ * chain). */
 int spai_engine_set_timing(spai_engine *eng, int enabled);
 /* ms[0] select, ms[1] evaluate (NN forward), ms[2] expand+backup; launches[3] */
 int spai_engine_timing(spai_engine *eng, double *avg_ms, double *launches);

@@ -194,7 +194,10 @@ int spai_engine_destroy(spai_engine *e) {
         B.value.release();
         B.iter_counts.release();
         B.iter_more.release();
+        B.iter_hits.release();
     }
+    e->cache.table.release();
+    e->cache.ctr.release();
     e->games.x.release();
     e->games.o.release();
     e->games.n.release();
@@ -333,7 +336,18 @@ int spai_engine_set_net(spai_engine *e, spai_net *n) {
     ENG_CHECK(e);
     SPAI_CHECK(!n || n->eng == e, SPAI_ERR_INVALID, "net belongs to another engine");
     e->net = n;
-    return SPAI_OK;
+    return eval_cache_clear(e);   // cached evaluations belong to the previous weights
+}
+
+int spai_eval_cache_set_capacity(spai_engine *e, uint64_t entries) {
+    ENG_CHECK(e);
+    return eval_cache_set_capacity(e, entries);
+}
+
+int spai_eval_cache_get_stats(spai_engine *e, spai_eval_cache_stats *out) {
+    ENG_CHECK(e);
+    PTR_CHECK(out);
+    return eval_cache_stats(e, out);
 }
 
 int spai_trees_create(spai_engine *e, uint32_t n) { ENG_CHECK(e); return trees_create(e, n); }
@@ -381,7 +395,7 @@ int spai_engine_set_timing(spai_engine *e, int enabled) {
     ENG_CHECK(e);
     KernelTimer &K = e->timer;
     K.enabled = enabled != 0;
-    K.stride = enabled > 1 ? (uint32_t)enabled : 4u;
+    K.stride = enabled > 1 ? (uint32_t)enabled : enabled < 0 ? 1u : 4u;
     for (int i = 0; i < 3; ++i) K.total_ms[i] = K.launches[i] = K.items[i] = 0;
     K.used = 0;
     K.which.clear();

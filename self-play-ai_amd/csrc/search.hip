@@ -58,6 +58,9 @@ struct TreeView {
 };
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
 
+// a hit of the evaluation cache: the tree's slot is in the batch's hit region (marked in T.slot)
+constexpr uint32_t kHitSlot = 0x80000000u;
+
 struct BatchView {
     uint32_t *count;
     uint32_t *more;   // tail mode: set when a tree stopped at the run cap with iterations left (else null)
@@ -65,7 +68,42 @@ struct BatchView {
     uint64_t *mine, *theirs;
     float *priors;
     float *value;
+    uint32_t *hits;   // evaluation cache: leaves served from it, in slots cap - 1 downwards (null: cache off)
+    uint32_t cap;
 };
+
+// ---------------------------------------------------------------- evaluation cache
+// A hash table in HBM from a leaf's full position (mine, theirs) to what the
+// evaluator wrote for it: the 7 masked priors and the value.  The evaluator's
+// output for a position depends on nothing but the position and the weights, so
+// a cached result is the recomputed one bit for bit.
+//
+// Layout: buckets of 8 ways (one per lane of a tree's group), 64 B per entry:
+//   word 0  mine   | gen << 49      the claim word (0: empty)
+//   word 1  theirs | gen << 49
+//   word 2  p0 p1 | word 3  p2 p3 | word 4  p4 p5 | word 5  p6 value
+// Every 8-byte word carries a non-zero mark: the generation (1..32767) above
+// the 49 board bits of the key words, the sign bit of the even prior (priors are
+// >= +0; an entry whose priors are not is never inserted) in the payload words.
+//
+// Protocol (no fence anywhere): an entry is claimed by one agent-scope CAS of
+// word 0 from empty and then written once, by the claimer alone; nothing is
+// overwritten until the table is cleared, and it is cleared only by a
+// stream-ordered memset while no search kernel runs.  So whatever a reader sees
+// of an entry -- its L1 is per CU, the L2s per XCD, the other chain may be
+// writing it right now -- is a subset of the entry's final words, the rest
+// zero.  The reader accepts only when all six words are marked and both key
+// words equal its own (full position and generation): then it holds exactly
+// the bytes one forward wrote for exactly this position.  Anything less reads
+// as a miss, and the leaf goes through the forward as before.
+struct CacheView {
+    uint4 *tab;      // null: off
+    uint32_t mask;   // buckets - 1
+    uint32_t gen;
+    uint32_t *ctr;   // [0] entries claimed since the clear, [1] dropped inserts
+};
+constexpr uint32_t kPriorMark = 0x80000000u;
+constexpr int kGenShift = 49;
 
 // PUCT score, mcts.rs:91-100, evaluated in the reference's operation order
 // (no contraction: built with -ffp-contract=off; sqrt and / correctly rounded).
@@ -250,17 +288,110 @@ __device__ __forceinline__ Descent descend(const TreeView &T, uint32_t t, const 
     return kLive;
 }
 
-// live leaf -> batch slot (mcts.rs:249-250)
-__device__ __forceinline__ void slot_leaf(const TreeView &T, const BatchView &B, uint32_t t, int lane8, uint64_t x,
-                                          uint64_t o, uint8_t n) {
+__device__ __forceinline__ uint4 *cache_way(const CacheView &C, uint64_t mine, uint64_t theirs, int way) {
+    const uint64_t h = c4::splitmix64(mine ^ (theirs * 0x9E3779B97F4A7C15ull));
+    const uint32_t bucket = (uint32_t)(h >> 32) & C.mask;
+    return C.tab + ((size_t)bucket * EvalCache::kWays + (uint32_t)way) * 4;
+}
+
+// Insert the evaluated leaf in slot s of batch B, by its tree's 8 lanes: each
+// reads one way's claim word; a way that already holds this position's word 0
+// ends it (the same position, or one that shares `mine` in this bucket: only an
+// insert is lost); else lane 0 claims the first empty way (going on to the next
+// when another writer got there first) and writes the entry.  A full bucket
+// drops the insert.  Returns true in lane 0 when an entry was claimed.
+__device__ __forceinline__ bool cache_insert(const CacheView &C, const BatchView &B, uint32_t s, int lane8) {
+    const uint64_t mine = B.mine[s], theirs = B.theirs[s];
+    const uint64_t gen = (uint64_t)C.gen << kGenShift;
+    const uint64_t k0 = mine | gen, k1 = theirs | gen;
+    uint4 *bucket = cache_way(C, mine, theirs, 0);
+    const uint64_t seen = *(const uint64_t *)(bucket + 4 * lane8);
+    const float4 pa = *(const float4 *)(B.priors + (size_t)s * kPriorStride);
+    const float4 pb = *(const float4 *)(B.priors + (size_t)s * kPriorStride + 4);
+    const float value = B.value[s];
+    const uint32_t same = group_bits(__ballot(seen == k0));
+    const uint32_t empty = group_bits(__ballot(seen == 0ull));
+    if (same || lane8 != 0) return false;
+    const uint32_t p0 = __float_as_uint(pa.x), p2 = __float_as_uint(pa.z), p4 = __float_as_uint(pb.x),
+                   p6 = __float_as_uint(pb.z);
+    bool claimed = false, skip = ((p0 | p2 | p4 | p6) & kPriorMark) != 0u;   // (a marked prior cannot be stored)
+    if (!skip)
+        for (int w = empty ? __ffs(empty) - 1 : (int)EvalCache::kWays; w < (int)EvalCache::kWays; ++w) {
+            uint4 *e = bucket + 4 * w;
+            const unsigned long long old = atomicCAS((unsigned long long *)e, 0ull, (unsigned long long)k0);
+            if (old == 0ull) {
+                ((uint64_t *)e)[1] = k1;
+                e[1] = make_uint4(p0 | kPriorMark, __float_as_uint(pa.y), p2 | kPriorMark, __float_as_uint(pa.w));
+                e[2] = make_uint4(p4 | kPriorMark, __float_as_uint(pb.y), p6 | kPriorMark, __float_as_uint(value));
+                claimed = true;
+                break;
+            }
+            if (old == k0) {
+                skip = true;
+                break;
+            }
+        }
+    if (!claimed && !skip) atomicAdd(C.ctr + 1, 1u);
+    return claimed;
+}
+// the fill counter, one atomic per wave: the wave's claims (lane 0 of each tree's group)
+__device__ __forceinline__ void cache_count(const CacheView &C, bool claimed) {
+    const uint64_t b = __ballot(claimed);
+    if (b && (threadIdx.x & 63) == (uint32_t)__ffsll((unsigned long long)__ballot(true)) - 1u)
+        atomicAdd(C.ctr, (uint32_t)c4::popc64(b));
+}
+
+// live leaf -> batch slot (mcts.rs:249-250).  With the evaluation cache, the
+// tree's 8 lanes first read the 8 ways of the position's bucket (one round
+// trip): when a way holds the position, complete, the leaf is served from it
+// -- a slot from the top of the batch (cap - 1 downwards, counted in B.hits),
+// with the position, priors and value the forward would have written there --
+// and the forward never sees it.  A chain's leaves of one iteration, hits and
+// misses together, are at most its trees (<= cap), so the two regions never meet.
+__device__ __forceinline__ void slot_leaf(const TreeView &T, const BatchView &B, const CacheView &C, uint32_t t,
+                                          int lane8, uint64_t x, uint64_t o, uint8_t n) {
+    const bool xm = c4::x_to_move(n);
+    const uint64_t mine = xm ? x : o, theirs = xm ? o : x;
+    if (lane8 == 0)
+        __hip_atomic_fetch_add(T.evals + t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // result unused: no wait
+    if (C.tab) {
+        const uint4 *e = cache_way(C, mine, theirs, lane8);
+        const uint4 q0 = e[0], q1 = e[1], q2 = e[2];
+        const uint64_t gen = (uint64_t)C.gen << kGenShift;
+        const bool match = (((uint64_t)q0.y << 32) | q0.x) == (mine | gen) &&
+                           (((uint64_t)q0.w << 32) | q0.z) == (theirs | gen) &&
+                           (q1.x & q1.z & q2.x & q2.z & kPriorMark) != 0u;
+        const uint32_t hit = group_bits(__ballot(match));
+        if (hit) {
+            // lane 0 takes the slot and records it (T.slot is lane 0's word: select_tree's
+            // kNoSlot store came from it too); the lane that holds the entry gets the slot
+            // from it and writes the payload
+            uint32_t slot = 0;
+            if (lane8 == 0) {
+                slot = B.cap - 1u - atomicAdd(B.hits, 1u);
+                T.slot[t] = slot | kHitSlot;
+                B.tree[slot] = t;
+                B.mine[slot] = mine;
+                B.theirs[slot] = theirs;
+            }
+            slot = (uint32_t)__shfl((int)slot, 0, kLanesPerTree);
+            if (lane8 == __ffs(hit) - 1) {
+                float4 *pr = (float4 *)(B.priors + (size_t)slot * kPriorStride);
+                pr[0] = make_float4(__uint_as_float(q1.x & ~kPriorMark), __uint_as_float(q1.y),
+                                    __uint_as_float(q1.z & ~kPriorMark), __uint_as_float(q1.w));
+                pr[1] = make_float4(__uint_as_float(q2.x & ~kPriorMark), __uint_as_float(q2.y),
+                                    __uint_as_float(q2.z & ~kPriorMark), 0.f);
+                B.value[slot] = __uint_as_float(q2.w);
+            }
+            return;
+        }
+    }
     if (lane8 == 0) {
         const uint32_t slot = atomicAdd(B.count, 1u);
-        __hip_atomic_fetch_add(T.evals + t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // result unused: no wait
-        const bool xm = c4::x_to_move(n);
         T.slot[t] = slot;
         B.tree[slot] = t;
-        B.mine[slot] = xm ? x : o;
-        B.theirs[slot] = xm ? o : x;
+        B.mine[slot] = mine;
+        B.theirs[slot] = theirs;
     }
 }
 
@@ -276,13 +407,13 @@ __device__ __forceinline__ void slot_leaf(const TreeView &T, const BatchView &B,
 // pass from lasting a solved tree's whole run while a tree that still evaluates
 // waits for the next one.
 template <bool RUN_ON>
-__device__ __forceinline__ void select_tree(const TreeView &T, const BatchView &B, uint32_t t, RootInfo &root,
-                                            int lane8, float c, uint32_t *err, uint32_t run_cap) {
+__device__ __forceinline__ void select_tree(const TreeView &T, const BatchView &B, const CacheView &C, uint32_t t,
+                                            RootInfo &root, int lane8, float c, uint32_t *err, uint32_t run_cap) {
     if (lane8 == 0) T.slot[t] = kNoSlot;
     uint64_t x, o;
     uint8_t n;
     if (!RUN_ON) {
-        if (descend(T, t, root, lane8, c, err, x, o, n) == kLive) slot_leaf(T, B, t, lane8, x, o, n);
+        if (descend(T, t, root, lane8, c, err, x, o, n) == kLive) slot_leaf(T, B, C, t, lane8, x, o, n);
         return;
     }
     uint32_t left = T.left[t];
@@ -293,7 +424,7 @@ __device__ __forceinline__ void select_tree(const TreeView &T, const BatchView &
         }
         --left;
         const Descent r = descend(T, t, root, lane8, c, err, x, o, n);
-        if (r == kLive) slot_leaf(T, B, t, lane8, x, o, n);
+        if (r == kLive) slot_leaf(T, B, C, t, lane8, x, o, n);
         if (r != kTerminal) break;
         root.rn += 1;   // the backup's visit of the root
         // the next descent reads records the other lanes of this tree just backed
@@ -362,8 +493,9 @@ __device__ __forceinline__ void expand_leaf(const TreeView &T, const BatchView &
 }
 
 template <bool RUN_ON>
-__global__ __launch_bounds__(kBlock) void k_select(TreeView T, BatchView B, const uint32_t *__restrict__ active,
-                                                   uint32_t n_active, float c, uint32_t *err, uint32_t run_cap) {
+__global__ __launch_bounds__(kBlock) void k_select(TreeView T, BatchView B, CacheView C,
+                                                   const uint32_t *__restrict__ active, uint32_t n_active, float c,
+                                                   uint32_t *err, uint32_t run_cap) {
     const uint32_t gi = (blockIdx.x * blockDim.x + threadIdx.x) / kLanesPerTree;
 #ifdef SPAI_TREE_PRIO
     __builtin_amdgcn_s_setprio(SPAI_TREE_PRIO);   // experiment: issue priority against the co-resident forward
@@ -371,7 +503,7 @@ __global__ __launch_bounds__(kBlock) void k_select(TreeView T, BatchView B, cons
     if (gi >= n_active) return;
     const uint32_t t = active[gi];
     RootInfo root = load_root(T, t);
-    select_tree<RUN_ON>(T, B, t, root, threadIdx.x & (kLanesPerTree - 1), c, err, run_cap);
+    select_tree<RUN_ON>(T, B, C, t, root, threadIdx.x & (kLanesPerTree - 1), c, err, run_cap);
 }
 
 // expand this iteration's leaf of every tree (batch `cur`), then select the next
@@ -381,7 +513,7 @@ __global__ __launch_bounds__(kBlock) void k_select(TreeView T, BatchView B, cons
 // loads above the stores), not a workgroup-scope one (s_waitcnt vmcnt(0): a
 // store round trip on every iteration's critical path).
 template <bool RUN_ON>
-__global__ __launch_bounds__(kBlock) void k_expand_select(TreeView T, BatchView cur, BatchView nxt,
+__global__ __launch_bounds__(kBlock) void k_expand_select(TreeView T, BatchView cur, BatchView nxt, CacheView C,
                                                           const uint32_t *__restrict__ active, uint32_t n_active,
                                                           float c, uint32_t *err, uint32_t run_cap) {
     const uint32_t gi = (blockIdx.x * blockDim.x + threadIdx.x) / kLanesPerTree;
@@ -402,11 +534,17 @@ __global__ __launch_bounds__(kBlock) void k_expand_select(TreeView T, BatchView 
                  "v"((uint32_t)root.o), "v"((uint32_t)(root.o >> 32)), "v"((uint32_t)root.n), "v"((uint32_t)root.status));
     asm volatile("" ::"v"(L.d), "v"(L.first), "v"(L.lv[0]), "v"(L.lv[1]), "v"(L.lv[2]), "v"(L.lv[3]), "v"(L.lv[4]),
                  "v"(L.lv[5]));
-    if (s != kNoSlot) expand_leaf(T, cur, t, s, lane8, err, L, root);
+    if (s != kNoSlot) expand_leaf(T, cur, t, s & ~kHitSlot, lane8, err, L, root);
     // the select reads records this tree's lanes just wrote: lanes of one wave,
     // whose memory operations are performed in order (no wait for the stores)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    select_tree<RUN_ON>(T, nxt, t, root, lane8, c, err, run_cap);
+    select_tree<RUN_ON>(T, nxt, C, t, root, lane8, c, err, run_cap);
+    // off the chain, after the select: the leaf the forward evaluated for this tree
+    // goes into the cache (a leaf served from it is there already)
+    if (C.tab) {
+        const bool claimed = s != kNoSlot && !(s & kHitSlot) && cache_insert(C, cur, s, lane8);
+        cache_count(C, claimed);
+    }
 }
 
 // tail mode: every active tree has all `iters` iterations of this search call ahead
@@ -428,23 +566,35 @@ __global__ __launch_bounds__(kBlock) void k_eval_stub(BatchView B, uint32_t max_
     B.value[s] = v;
 }
 
-__global__ __launch_bounds__(kBlock) void k_expand(TreeView T, BatchView B, uint32_t max_n, uint32_t *err) {
-    const uint32_t s = (blockIdx.x * blockDim.x + threadIdx.x) / kLanesPerTree;
-    if (s >= max_n || s >= *B.count) return;
+// the last iteration's expansion, per leaf: the forwarded leaves in slots [0, count),
+// then those served from the evaluation cache in slots cap - 1 downwards
+__global__ __launch_bounds__(kBlock) void k_expand(TreeView T, BatchView B, CacheView C, uint32_t max_n,
+                                                   uint32_t *err) {
+    const uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) / kLanesPerTree;
+    if (i >= max_n) return;
+    const uint32_t count = *B.count, hits = B.hits ? *B.hits : 0u;
+    if (i >= count + hits) return;
+    const bool fwd = i < count;
+    const uint32_t s = fwd ? i : B.cap - 1u - (i - count);
     const int lane8 = threadIdx.x & (kLanesPerTree - 1);
     const uint32_t t = B.tree[s];
     RootInfo root{};   // (the root's record is not needed after the last expansion)
     expand_leaf(T, B, t, s, lane8, err, load_leaf_path(T, t, lane8), root);
+    if (C.tab) {
+        const bool claimed = fwd && cache_insert(C, B, s, lane8);
+        cache_count(C, claimed);
+    }
 }
 
 // per active tree: [0] = root first|nch<<24 (children word), [1..7] child visit counts;
-// max_evals: the most live leaves one tree evaluated in this search call
+// max_evals[0]: the most live leaves one tree evaluated in this search call, [1]: their sum over the trees
 __global__ void k_root_stats(TreeView T, const uint32_t *__restrict__ active, uint32_t n_active, uint32_t *out,
                              uint32_t *max_evals) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_active) return;
     const uint32_t t = active[i];
     atomicMax(max_evals, T.evals[t]);
+    atomicAdd(max_evals + 1, T.evals[t]);
     const uint4 *nodes = T.nodes + (size_t)t * T.cap;
     const uint4 r = nodes[T.root[t]];
     out[i * 8] = r.w;
@@ -460,7 +610,8 @@ __global__ void k_root_stats(TreeView T, const uint32_t *__restrict__ active, ui
 // back to the host: [0] the root's children word, [1..7] the child visit counts,
 // [8] the pick (index | action << 8 | new status << 16; without one, bit 31 and
 // the weighted_index code, or kPickNoTable for a visit count beyond the table),
-// [9] the tree's live leaves of the call.  out[0] gets the error flags, and
+// [9] the tree's live leaves of the call.  out[0] gets the error flags, out[1] the
+// evaluation cache's fill, and
 // block 0 copies every chain's per-iteration leaf counts after the records, so
 // one copy brings back everything the host needs.
 constexpr int kMoveRec = 10;
@@ -476,12 +627,13 @@ struct ChainCounts {
 __global__ void k_advance(TreeView T, RootsOut R, const uint32_t *__restrict__ active, uint32_t n_active,
                           const float *__restrict__ pow_tab, uint32_t pow_n, uint64_t seed,
                           const uint64_t *__restrict__ slot_gid, uint32_t *__restrict__ slot_move,
-                          const uint32_t *err, ChainCounts cc, int nchain, uint32_t n_counts, uint32_t *out) {
+                          const uint32_t *err, const uint32_t *cache_fill, ChainCounts cc, int nchain,
+                          uint32_t n_counts, uint32_t *out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (blockIdx.x == 0) {
         if (threadIdx.x == 0) {
             out[0] = *err;
-            out[1] = 0;
+            out[1] = cache_fill ? *cache_fill : 0u;
         }
         uint32_t *counts = out + 2 + (size_t)n_active * kMoveRec;
         for (int h = 0; h < nchain; ++h)
@@ -567,7 +719,89 @@ BatchView batch_view(spai_engine *e, int chain, uint32_t it) {
     Batch &B = e->batch[chain];
     const size_t h = (size_t)(it & 1u) * B.cap;
     return BatchView{B.iter_counts.p + it, B.iter_more.p ? B.iter_more.p + it : nullptr, B.tree.p + h, B.mine.p + h, B.theirs.p + h,
-                     B.priors.p + h * kPriorStride, B.value.p + h};
+                     B.priors.p + h * kPriorStride, B.value.p + h,
+                     e->cache.buckets && B.iter_hits.p ? B.iter_hits.p + it : nullptr, B.cap};
+}
+
+CacheView cache_view(spai_engine *e) {
+    EvalCache &C = e->cache;
+    if (!C.buckets) return CacheView{nullptr, 0u, 0u, nullptr};
+    return CacheView{C.table.p, C.buckets - 1u, C.gen, C.ctr.p};
+}
+
+// Empty the table on the engine stream: every search call's chains are joined to it
+// before the call returns and forked from it when the next one starts, so no search
+// kernel runs while the memset does.  A new generation goes with every clear.
+int cache_clear(spai_engine *e) {
+    EvalCache &C = e->cache;
+    if (!C.buckets) return SPAI_OK;
+    uint32_t fill = 0;
+    SPAI_HIP(hipMemcpyAsync(&fill, C.ctr.p, 4, hipMemcpyDeviceToHost, e->stream));
+    SPAI_HIP(hipStreamSynchronize(e->stream));
+    C.inserts_cleared += fill;
+    SPAI_HIP(hipMemsetAsync(C.table.p, 0, C.table.n * sizeof(uint4), e->stream));
+    SPAI_HIP(hipMemsetAsync(C.ctr.p, 0, 4, e->stream));
+    C.gen = C.gen % 32767u + 1u;
+    C.fill_seen = 0;
+    C.clears += 1;
+    return SPAI_OK;
+}
+
+// Resolve the capacity (spai_eval_cache_set_capacity, else SPAI_EVAL_CACHE=<entries>, else
+// kEntriesPerTree per tree slot of max_trees) and allocate the table, on the first search
+// call after a change; on for the net evaluator only.  The counters outlive a resize:
+// the old table's claims are added to the host's total and the device count starts again.
+int cache_prepare(spai_engine *e) {
+    EvalCache &C = e->cache;
+    if (C.ready) return SPAI_OK;
+    uint64_t want = 0;
+    if (e->cfg.eval == SPAI_EVAL_NET) {
+        const char *v = std::getenv("SPAI_EVAL_CACHE");
+        if (C.user_set) want = C.requested;
+        else if (v) want = std::strtoull(v, nullptr, 10);
+        else want = std::min<uint64_t>(EvalCache::kEntriesPerTree * std::max(1u, e->cfg.max_trees),
+                                       EvalCache::kDefaultMaxEntries);
+    }
+    uint32_t buckets = 0;
+    if (want) {
+        buckets = 1;
+        while ((uint64_t)buckets * 2 * EvalCache::kWays <= want && buckets < (1u << 28)) buckets *= 2;
+    }
+    if (buckets != C.buckets) {
+        SPAI_HIP(hipStreamSynchronize(e->stream));
+        if (C.buckets) {   // the old table's claims leave with it
+            uint32_t fill = 0;
+            SPAI_HIP(hipMemcpy(&fill, C.ctr.p, 4, hipMemcpyDeviceToHost));
+            C.inserts_cleared += fill;
+        }
+        C.buckets = 0;
+        if (C.ctr.p) SPAI_HIP(hipMemsetAsync(C.ctr.p, 0, 4, e->stream));
+        // the default size is a wish: where the device has no room for it the table is
+        // halved until it fits, and below kMinDefaultBuckets the cache stays off (the
+        // search does not need it).  A size the caller asked for fits or is an error.
+        const bool by_default = !C.user_set && !std::getenv("SPAI_EVAL_CACHE");
+        int rc = C.table.alloc((size_t)buckets * EvalCache::kWays * 4);
+        while (rc != SPAI_OK && by_default) {
+            (void)hipGetLastError();
+            buckets = buckets / 2 >= EvalCache::kMinDefaultBuckets ? buckets / 2 : 0;
+            rc = C.table.alloc((size_t)buckets * EvalCache::kWays * 4);
+        }
+        SPAI_TRY(rc);
+        if (buckets) {
+            if (!C.ctr.p) {
+                SPAI_TRY(C.ctr.alloc(2));
+                SPAI_HIP(hipMemsetAsync(C.ctr.p, 0, 8, e->stream));
+            }
+            C.buckets = buckets;
+            SPAI_HIP(hipMemsetAsync(C.ctr.p, 0, 4, e->stream));
+            SPAI_HIP(hipMemsetAsync(C.table.p, 0, C.table.n * sizeof(uint4), e->stream));
+            C.gen = C.gen % 32767u + 1u;
+            C.fill_seen = 0;
+            C.clears += 1;
+        }
+    }
+    C.ready = true;
+    return SPAI_OK;
 }
 
 // Number of search chains for n trees: two halves when each half still fills
@@ -709,7 +943,7 @@ int trees_create(spai_engine *e, uint32_t n) {
         SPAI_TRY(T.depth.alloc(n));
         SPAI_TRY(T.slot.alloc(n));
         SPAI_TRY(T.left.alloc(n));
-        SPAI_TRY(T.evals.alloc(n + 1));   // [n]: the search call's max over trees (k_root_stats)
+        SPAI_TRY(T.evals.alloc(n + 2));   // [n], [n + 1]: the search call's max and sum over trees (k_root_stats)
         SPAI_TRY(T.slot_gid.alloc(n));
         SPAI_TRY(T.slot_move.alloc(n));
         SPAI_TRY(T.refill.alloc(2 * (size_t)n));
@@ -727,6 +961,7 @@ int trees_create(spai_engine *e, uint32_t n) {
         T.cap = (uint32_t)cap;
     }
     e->last_evals_per_iter = -1;   // a fresh set of trees: no per-iteration statistics yet
+    e->last_served_per_iter = -1;
     e->last_max_tree_evals = ~0u;
     T.h_root.assign(n, 0);
     T.h_root_state.assign(n, c4::State{0, 0, 0, c4::kOngoing});
@@ -778,6 +1013,10 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
     Trees &T = e->trees;
     const int kind = (int)e->cfg.eval;
     hipStream_t st = e->stream;
+    // evaluation cache: allocated on first use; emptied here, between search calls
+    // (no chain runs), once it is more than 3/4 full, so a long stream keeps hitting
+    SPAI_TRY(cache_prepare(e));
+    if (e->cache.buckets && (uint64_t)e->cache.fill_seen * 4 > e->cache.entries() * 3) SPAI_TRY(cache_clear(e));
     // tail mode (select_tree RUN_ON, one chain): late in a game, when in the previous
     // search call of these trees no tree evaluated SPAI_TAIL_TREE_EVALS leaves or
     // more (a pass per live leaf of the busiest tree: few passes), or the call
@@ -787,11 +1026,13 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
     const char *tt_env = std::getenv("SPAI_TAIL_TREE_EVALS");
     const double tail_leaves = tl_env ? std::atof(tl_env) : kTailLeaves;
     const uint32_t tail_tree = tt_env ? (uint32_t)std::max(0, std::atoi(tt_env)) : kTailTreeEvals;
-    const bool tail = num_searches > 0 && e->last_evals_per_iter >= 0 &&
-                      (e->last_evals_per_iter < tail_leaves || e->last_max_tree_evals < tail_tree);
+    // (a tree's passes are its live leaves, whether the forward or the evaluation cache
+    // answers them: the served leaves decide here, the forwarded ones in chains_for)
+    const bool tail = num_searches > 0 && e->last_served_per_iter >= 0 &&
+                      (e->last_served_per_iter < tail_leaves || e->last_max_tree_evals < tail_tree);
     // the run cap; after a call that evaluated nothing (every tree solved: no tree
     // to keep waiting) none, and a check after every pass -- normally one
-    const bool solved = e->last_evals_per_iter == 0.0;
+    const bool solved = e->last_served_per_iter == 0.0;
     const char *tr_env = std::getenv("SPAI_TAIL_RUN");
     const uint32_t tail_run =
         tr_env ? (uint32_t)std::max(1, std::atoi(tr_env)) : (solved ? std::max(num_searches, 1u) : kTailRun);
@@ -815,6 +1056,10 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
         const uint32_t nc = std::max<uint32_t>(num_searches, 1) + (tail ? kTailChunk + 1 : 0);
         if (B.iter_counts.n < nc) SPAI_TRY(B.iter_counts.alloc(nc));
         SPAI_HIP(hipMemsetAsync(B.iter_counts.p, 0, (size_t)nc * 4, st));
+        if (e->cache.buckets) {   // the per-iteration counters of the leaves served from the cache
+            if (B.iter_hits.n < nc) SPAI_TRY(B.iter_hits.alloc(nc));
+            SPAI_HIP(hipMemsetAsync(B.iter_hits.p, 0, (size_t)nc * 4, st));
+        }
         if (tail) {
             if (B.iter_more.n < nc) SPAI_TRY(B.iter_more.alloc(nc));
             SPAI_HIP(hipMemsetAsync(B.iter_more.p, 0, (size_t)nc * 4, st));
@@ -822,12 +1067,13 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
     }
     SPAI_HIP(hipMemcpyAsync(e->active.p, tree_idx, n * 4, hipMemcpyHostToDevice, st));
     SPAI_HIP(hipMemsetAsync(e->err.p, 0, 4, st));
-    SPAI_HIP(hipMemsetAsync(T.evals.p, 0, ((size_t)T.n_trees + 1) * 4, st));
+    SPAI_HIP(hipMemsetAsync(T.evals.p, 0, ((size_t)T.n_trees + 2) * 4, st));
     if (nchain > 1) {   // fork: chains 1.. start after the setup on the engine stream
         SPAI_HIP(hipEventRecord(e->ev_fork, st));
         for (int h = 1; h < nchain; ++h) SPAI_HIP(hipStreamWaitEvent(e->chain_stream[h], e->ev_fork, 0));
     }
     const TreeView tv = tree_view(e);
+    const CacheView cv = cache_view(e);
     const bool timed = e->timer.enabled && !tail;   // samples every chain's launches every stride-th iteration
     uint32_t &n_counts = R.n_counts;   // leaf counters to read back per chain
     n_counts = num_searches;
@@ -841,8 +1087,8 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
         const uint32_t g8 = (n + kTreesPerBlock - 1) / kTreesPerBlock;
         const uint32_t *act = e->active.p;
         k_set_left<<<(n + 255) / 256, 256, 0, st>>>(tv, act, n, num_searches);
-        k_select<true><<<g8, kBlock, 0, st>>>(tv, batch_view(e, 0, 0), act, n, e->cfg.c, e->err.p, tail_run);
-        uint32_t p = 0, next = 1, more = 0;
+        k_select<true><<<g8, kBlock, 0, st>>>(tv, batch_view(e, 0, 0), cv, act, n, e->cfg.c, e->err.p, tail_run);
+        uint32_t p = 0, next = 1, more = 0, next_hits = 0;
         for (;;) {
             for (uint32_t q = 0; q < tail_chunk; ++q, ++p) {
                 const BatchView bv = batch_view(e, 0, p);
@@ -851,13 +1097,16 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
                 } else {
                     k_eval_stub<<<(n + kBlock - 1) / kBlock, kBlock, 0, st>>>(bv, n, kind);
                 }
-                k_expand_select<true><<<g8, kBlock, 0, st>>>(tv, bv, batch_view(e, 0, p + 1), act, n, e->cfg.c,
+                k_expand_select<true><<<g8, kBlock, 0, st>>>(tv, bv, batch_view(e, 0, p + 1), cv, act, n, e->cfg.c,
                                                              e->err.p, tail_run);
             }
             SPAI_HIP(hipGetLastError());
             SPAI_HIP(hipMemcpyAsync(&next, e->batch[0].iter_counts.p + p, 4, hipMemcpyDeviceToHost, st));
             SPAI_HIP(hipMemcpyAsync(&more, e->batch[0].iter_more.p + p, 4, hipMemcpyDeviceToHost, st));
+            if (cv.tab)   // a leaf served from the evaluation cache stops its tree's pass like a forwarded one
+                SPAI_HIP(hipMemcpyAsync(&next_hits, e->batch[0].iter_hits.p + p, 4, hipMemcpyDeviceToHost, st));
             SPAI_HIP(hipStreamSynchronize(st));
+            next += next_hits;
             if (next == 0 && more == 0) break;   // pass p has nothing to evaluate and no tree was capped: all done
             SPAI_CHECK(p <= num_searches + 1, SPAI_ERR_INVALID, "internal: tail passes exceed the iterations");
             // this chunk's counters are read back below; the next chunk's are fresh
@@ -877,7 +1126,7 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
             const bool sample = timed && (it % e->timer.stride == 0);
             if (it == 0) {
                 if (sample) SPAI_TRY(timer_record(e, 0, it, true, sh, h));
-                k_select<false><<<g8, kBlock, 0, sh>>>(tv, bv, act, nh, e->cfg.c, e->err.p, 0u);
+                k_select<false><<<g8, kBlock, 0, sh>>>(tv, bv, cv, act, nh, e->cfg.c, e->err.p, 0u);
                 if (sample) SPAI_TRY(timer_record(e, 0, it, false, sh, h));
             }
             if (sample) SPAI_TRY(timer_record(e, 1, it, true, sh, h));
@@ -891,12 +1140,12 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
             if (it + 1 < num_searches) {
                 const bool s2 = timed && ((it + 1) % e->timer.stride == 0);
                 if (s2) SPAI_TRY(timer_record(e, 0, it + 1, true, sh, h));
-                k_expand_select<false><<<g8, kBlock, 0, sh>>>(tv, bv, batch_view(e, h, it + 1), act, nh,
+                k_expand_select<false><<<g8, kBlock, 0, sh>>>(tv, bv, batch_view(e, h, it + 1), cv, act, nh,
                                                               e->cfg.c, e->err.p, 0u);
                 if (s2) SPAI_TRY(timer_record(e, 0, it + 1, false, sh, h));
             } else {
                 if (sample) SPAI_TRY(timer_record(e, 2, it, true, sh, h));
-                k_expand<<<g8, kBlock, 0, sh>>>(tv, bv, nh, e->err.p);
+                k_expand<<<g8, kBlock, 0, sh>>>(tv, bv, cv, nh, e->err.p);
                 if (sample) SPAI_TRY(timer_record(e, 2, it, false, sh, h));
             }
         }
@@ -912,8 +1161,13 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
 // The call's bookkeeping once its counters [chain][n_counts], error flags and
 // largest per-tree leaf count are on the host: timers, the device errors, and the
 // statistics the next call's chain and tail policies read.
+// `served`: the call's live leaves, those answered by the evaluation cache included
+// (the statistic `evals`); the counters hold the leaves the forward ran, which is what
+// the launches cost and so what the chain and group-size policies go by.  The tail-mode
+// policy goes by the served leaves: a tree's tail passes are its live leaves, whoever
+// answers them.
 int search_finish(spai_engine *e, const SearchRun &R, uint32_t num_searches, const uint32_t *ch_counts, uint32_t err,
-                  uint32_t max_tree_evals, double *evals_out) {
+                  uint32_t max_tree_evals, double served, uint32_t cache_fill, double *evals_out) {
     SPAI_TRY(timer_collect(e, ch_counts, R.n_counts, R.cnt));
     double s = 0;
     for (int h = 0; h < R.nchain; ++h)
@@ -921,8 +1175,14 @@ int search_finish(spai_engine *e, const SearchRun &R, uint32_t num_searches, con
     SPAI_CHECK(!(err & kErrCapacity), SPAI_ERR_CAPACITY, "node arena full (cap %u per tree)", e->trees.cap);
     SPAI_CHECK(!(err & kErrDepth), SPAI_ERR_CAPACITY, "tree deeper than %d", kMaxDepth);
     SPAI_CHECK(!(err & kErrNan), SPAI_ERR_NAN, "NaN UCB in select (reference: partial_cmp().unwrap() panics)");
-    if (evals_out) *evals_out = s;
+    if (evals_out) *evals_out = served;
+    if (e->cache.buckets) {
+        e->cache.lookups += served;
+        e->cache.hits += served - s;
+        e->cache.fill_seen = cache_fill;
+    }
     e->last_evals_per_iter = num_searches ? s / num_searches : -1;
+    e->last_served_per_iter = num_searches ? served / num_searches : -1;
     e->last_max_tree_evals = max_tree_evals;
     return SPAI_OK;
 }
@@ -946,16 +1206,18 @@ int search(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_se
     k_root_stats<<<(n + 255) / 256, 256, 0, st>>>(tv, e->active.p, n, e->stats.p, T.evals.p + T.n_trees);
     SPAI_HIP(hipGetLastError());
     std::vector<uint32_t> stats((size_t)n * 8), ch_counts((size_t)nchain * n_counts);
-    uint32_t err = 0, max_tree_evals = 0;
+    uint32_t err = 0, tree_evals[2] = {0, 0}, cache_fill = 0;   // the trees' max and sum
     SPAI_HIP(hipMemcpyAsync(stats.data(), e->stats.p, stats.size() * 4, hipMemcpyDeviceToHost, st));
-    SPAI_HIP(hipMemcpyAsync(&max_tree_evals, T.evals.p + T.n_trees, 4, hipMemcpyDeviceToHost, st));
+    SPAI_HIP(hipMemcpyAsync(tree_evals, T.evals.p + T.n_trees, 8, hipMemcpyDeviceToHost, st));
+    if (e->cache.buckets) SPAI_HIP(hipMemcpyAsync(&cache_fill, e->cache.ctr.p, 4, hipMemcpyDeviceToHost, st));
     if (n_counts)
         for (int h = 0; h < nchain; ++h)
             SPAI_HIP(hipMemcpyAsync(ch_counts.data() + (size_t)h * n_counts, e->batch[h].iter_counts.p,
                                     n_counts * 4, hipMemcpyDeviceToHost, st));
     SPAI_HIP(hipMemcpyAsync(&err, e->err.p, 4, hipMemcpyDeviceToHost, st));
     SPAI_HIP(hipStreamSynchronize(st));
-    SPAI_TRY(search_finish(e, R, num_searches, ch_counts.data(), err, max_tree_evals, evals_out));
+    SPAI_TRY(search_finish(e, R, num_searches, ch_counts.data(), err, tree_evals[0], (double)tree_evals[1], cache_fill,
+                           evals_out));
     // root visit policy (mcts.rs:310-331)
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t t = tree_idx[i];
@@ -1121,8 +1383,9 @@ int selfplay_run(spai_engine *e, uint32_t n_games, uint64_t gid_base, spai_sampl
         ChainCounts cc{};
         for (int h = 0; h < R.nchain; ++h) cc.p[h] = e->batch[h].iter_counts.p;
         k_advance<<<(na + 63) / 64, 64, 0, st>>>(tv, ro, e->active.p, na, e->pow_tab.p, (uint32_t)e->pow_tab.n,
-                                                 e->cfg.seed, T.slot_gid.p, T.slot_move.p, e->err.p, cc, R.nchain,
-                                                 R.n_counts, e->move_out.p);
+                                                 e->cfg.seed, T.slot_gid.p, T.slot_move.p, e->err.p,
+                                                 e->cache.buckets ? e->cache.ctr.p : nullptr, cc, R.nchain, R.n_counts,
+                                                 e->move_out.p);
         SPAI_HIP(hipGetLastError());
         const size_t words = 2 + (size_t)na * kMoveRec + (size_t)R.nchain * R.n_counts;
         SPAI_HIP(hipMemcpyAsync(dst, e->move_out.p, words * 4, hipMemcpyDeviceToHost, st));
@@ -1151,14 +1414,17 @@ int selfplay_run(spai_engine *e, uint32_t n_games, uint64_t gid_base, spai_sampl
         const auto tm1 = std::chrono::steady_clock::now();
         const uint32_t passes = e->last_tail_passes;
         uint32_t max_ev = 0;
+        double served = 0;   // live leaves of the call over its trees (hits of the evaluation cache included)
         bool stop = false;   // a game without a move: its error is raised in the bookkeeping below
         for (uint32_t i = 0; i < na; ++i) {
             const uint32_t *rec = mo + 2 + (size_t)i * kMoveRec;
             max_ev = std::max(max_ev, rec[9]);
+            served += rec[9];
             stop |= (rec[8] & kPickNone) != 0;
         }
         double ev = 0;
-        SPAI_TRY(search_finish(e, R, ns, mo + 2 + (size_t)na * kMoveRec, mo[0], max_ev, &ev));
+        SPAI_TRY(search_finish(e, R, ns, mo + 2 + (size_t)na * kMoveRec, mo[0], max_ev, served, mo[1], &ev));
+        const double fwd_leaves = e->last_evals_per_iter * ns;
         sims += (double)na * ns;
         evals += ev;
         moves += 1;
@@ -1262,11 +1528,12 @@ int selfplay_run(spai_engine *e, uint32_t n_games, uint64_t gid_base, spai_sampl
         }
         if (trace)   // move, active trees, leaves evaluated, search seconds (launch to records), host seconds
                      // between the records and the next launch, search passes (tail mode; 0: one launch pair
-                     // per iteration), bookkeeping seconds (overlapping the next search)
-            std::fprintf(trace, "%llu,%u,%.0f,%.6f,%.6f,%u,%.6f\n", (unsigned long long)move_no, na, ev,
+                     // per iteration), bookkeeping seconds (overlapping the next search), leaves the forward
+                     // ran (the rest of the evaluated ones came from the evaluation cache)
+            std::fprintf(trace, "%llu,%u,%.0f,%.6f,%.6f,%u,%.6f,%.0f\n", (unsigned long long)move_no, na, ev,
                          std::chrono::duration<double>(tm1 - tm0).count(),
                          std::chrono::duration<double>(tm2 - tm1).count(), passes,
-                         std::chrono::duration<double>(std::chrono::steady_clock::now() - tm3).count());
+                         std::chrono::duration<double>(std::chrono::steady_clock::now() - tm3).count(), fwd_leaves);
         tm0 = tm2;
         cur ^= 1;
         ++move_no;
@@ -1279,6 +1546,29 @@ int selfplay_run(spai_engine *e, uint32_t n_games, uint64_t gid_base, spai_sampl
         stats->moves = moves;
         stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     }
+    return SPAI_OK;
+}
+
+int eval_cache_set_capacity(spai_engine *e, uint64_t entries) {
+    e->cache.user_set = true;
+    e->cache.requested = entries;
+    e->cache.ready = false;   // resolved, and the table resized, at the next search call
+    return SPAI_OK;
+}
+
+int eval_cache_clear(spai_engine *e) { return cache_clear(e); }
+
+int eval_cache_stats(spai_engine *e, spai_eval_cache_stats *out) {
+    EvalCache &C = e->cache;
+    uint32_t ctr[2] = {0, 0};
+    SPAI_HIP(hipStreamSynchronize(e->stream));
+    if (C.ctr.p) SPAI_HIP(hipMemcpy(ctr, C.ctr.p, 8, hipMemcpyDeviceToHost));
+    out->lookups = C.lookups;
+    out->hits = C.hits;
+    out->inserts = C.inserts_cleared + ctr[0];
+    out->dropped = ctr[1];
+    out->clears = C.clears;
+    out->capacity = (double)C.entries();
     return SPAI_OK;
 }
 

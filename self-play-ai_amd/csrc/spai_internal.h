@@ -104,6 +104,28 @@ struct Batch {
     DevBuf<float> value;            // [cap]
     DevBuf<uint32_t> iter_counts;   // per-iteration leaf counts of the current search
     DevBuf<uint32_t> iter_more;     // tail mode: per pass, set if a tree stopped at the run cap
+    DevBuf<uint32_t> iter_hits;     // evaluation cache: per-iteration count of leaves served from it (slots from the top)
+};
+
+// Evaluation cache of the Connect4 search (search.hip "evaluation cache"): a hash
+// table in HBM from the full leaf position (mine, theirs) to the evaluator's 7
+// masked priors and value, valid for one weight set.  8-way buckets of 64-B
+// entries; insert-only between clears.
+struct EvalCache {
+    static constexpr uint32_t kWays = 8;
+    static constexpr uint64_t kEntriesPerTree = 16384;    // default capacity per tree slot (cfg.max_trees): 1 MiB
+    static constexpr uint64_t kDefaultMaxEntries = 1ull << 26;   // 4 GiB
+    static constexpr uint32_t kMinDefaultBuckets = 1024;  // a default table that does not fit is halved down to this
+    bool user_set = false;          // capacity set through spai_eval_cache_set_capacity (else SPAI_EVAL_CACHE / default)
+    uint64_t requested = 0;         // user_set: entries asked for (0: off)
+    bool ready = false;             // capacity resolved and the table allocated (or the cache off)
+    uint32_t buckets = 0;           // power of two; 0: off
+    uint32_t gen = 0;               // weight/epoch generation in the key words' spare bits, 1..32767
+    DevBuf<uint4> table;            // [buckets][kWays][4]
+    DevBuf<uint32_t> ctr;           // [0] entries claimed since the last clear, [1] inserts dropped (ever)
+    uint32_t fill_seen = 0;         // ctr[0] as of the end of the latest search call
+    double lookups = 0, hits = 0, inserts_cleared = 0, clears = 0;   // host totals (inserts: + ctr[0])
+    uint64_t entries() const { return (uint64_t)buckets * kWays; }
 };
 
 struct KernelTimer {
@@ -212,7 +234,8 @@ struct spai_engine {
     spai::Batch batch[kChains];
     hipStream_t chain_stream[kChains] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[kChains] = {nullptr, nullptr, nullptr, nullptr};
-    double last_evals_per_iter = -1;   // previous search call's mean leaves per iteration (< 0: none yet)
+    double last_evals_per_iter = -1;   // previous search call's mean forwarded leaves per iteration (< 0: none yet)
+    double last_served_per_iter = -1;  // the same with the leaves served from the evaluation cache (tail-mode policy)
     uint32_t last_tail_passes = 0;     // previous search call's tail-mode passes (0: not in tail mode)
     uint32_t last_max_tree_evals = ~0u;   // previous search call's most live leaves of one tree (~0: none yet)
     spai_net *net = nullptr;
@@ -228,6 +251,7 @@ struct spai_engine {
     uint32_t *h_move[2] = {nullptr, nullptr};
     size_t h_move_n = 0;
     spai::KernelTimer timer;
+    spai::EvalCache cache;
 };
 
 namespace spai {
@@ -310,6 +334,11 @@ int tree_node(spai_engine *e, uint32_t t, uint32_t node, spai_c4_state *st, uint
 int tree_size(spai_engine *e, uint32_t t, uint32_t *nodes);
 int selfplay_run(spai_engine *e, uint32_t n_games, uint64_t gid_base, spai_sample_sink sink, void *user,
                  spai_selfplay_stats *stats, uint32_t window = 0);
+// evaluation cache: capacity in entries (0: off), takes effect at the next search call;
+// clear it (weights changed: always with a new generation); counters
+int eval_cache_set_capacity(spai_engine *e, uint64_t entries);
+int eval_cache_clear(spai_engine *e);
+int eval_cache_stats(spai_engine *e, spai_eval_cache_stats *out);
 
 inline c4::State from_abi(const spai_c4_state &s) { return c4::State{s.x, s.o, s.num_actions_played, s.status}; }
 inline spai_c4_state to_abi(const c4::State &s) {

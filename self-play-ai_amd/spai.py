@@ -32,7 +32,8 @@ SYMBOLS = [
     "spai_mask_invalid", "spai_rules_bench", "spai_net_num_params", "spai_net_init_params", "spai_net_create",
     "spai_net_destroy", "spai_net_forward", "spai_predict", "spai_engine_set_net", "spai_trees_create",
     "spai_tree_reset", "spai_search", "spai_tree_use_subtree", "spai_tree_node", "spai_tree_size",
-    "spai_selfplay_run", "spai_selfplay_stream", "spai_engine_set_timing", "spai_engine_timing", "spai_engine_timing_items",
+    "spai_selfplay_run", "spai_selfplay_stream", "spai_eval_cache_set_capacity", "spai_eval_cache_get_stats",
+    "spai_engine_set_timing", "spai_engine_timing", "spai_engine_timing_items",
     "spai_net_phase_cycles", "spai_net_bench", "spai_net_bench_conc", "spai_adam_config_default", "spai_learner_create", "spai_learner_destroy",
     "spai_learner_train_batch", "spai_learner_train_batches", "spai_learner_params", "spai_learner_grads", "spai_learner_activation", "spai_comm_unique_id",
     "spai_learner_set_comm", "spai_learner_broadcast", "spai_learner_set_host_comm", "spai_learner_last_batch",
@@ -80,6 +81,10 @@ class Config(C.Structure):
 
 class SelfPlayStats(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("sims", "evals", "games", "positions", "moves", "seconds")]
+
+
+class EvalCacheStats(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("lookups", "hits", "inserts", "dropped", "clears", "capacity")]
 
 
 class AdamConfig(C.Structure):
@@ -165,6 +170,8 @@ def lib():
         L.spai_tree_size.argtypes = [vp, u32, vp]
         L.spai_selfplay_run.argtypes = [vp, u32, u64, SINK, vp, P(SelfPlayStats)]
         L.spai_selfplay_stream.argtypes = [vp, u32, u32, u64, SINK, vp, P(SelfPlayStats)]
+        L.spai_eval_cache_set_capacity.argtypes = [vp, u64]
+        L.spai_eval_cache_get_stats.argtypes = [vp, P(EvalCacheStats)]
         L.spai_engine_set_timing.argtypes = [vp, i32]
         L.spai_engine_timing.argtypes = [vp, vp, vp]
         L.spai_engine_timing_items.argtypes = [vp, vp, vp]
@@ -435,10 +442,22 @@ class Engine:
             _check(lib().spai_selfplay_stream(self.h, n_games, window, game_id_base, cb, None, C.byref(st)))
         return games, {k: getattr(st, k) for k, _ in SelfPlayStats._fields_}
 
+    # ---- evaluation cache (EVAL_NET: positions the net has seen under the current weights)
+    def set_eval_cache(self, entries):
+        """capacity in entries from the next search call on (0: off)"""
+        _check(lib().spai_eval_cache_set_capacity(self.h, int(entries)))
+
+    def eval_cache_stats(self):
+        st = EvalCacheStats()
+        _check(lib().spai_eval_cache_get_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in EvalCacheStats._fields_}
+
     # ---- profiling
     def set_timing(self, on, stride=None):
-        """on: enable the sampled HIP events; stride: sample every stride-th iteration (default 4)"""
-        _check(lib().spai_engine_set_timing(self.h, (int(stride) if stride and stride > 1 else 1) if on else 0))
+        """on: enable the sampled HIP events; stride: sample every stride-th iteration (default 4;
+        1: every iteration)"""
+        k = 1 if not stride else -1 if stride == 1 else int(stride)
+        _check(lib().spai_engine_set_timing(self.h, k if on else 0))
 
     def timing(self):
         avg = np.zeros(3, np.float64)
