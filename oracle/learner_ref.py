@@ -122,6 +122,36 @@ def train_step_dp(params, adam_m, adam_v, step, rank_batches, blocks, hidden, lr
     return P, m, vv, [p[2] for p in parts], G, [p[1] for p in parts]
 
 
+# The three sums of the step that a device kernel spreads over loops of its own
+# (the register part and the re-read part of the BatchNorm kernels, the chunk sum
+# of the weight gradient) and the two places where a factor can be lost.  They are
+# module-level so that tests/test_learner_ref_cpu.py can swap in deliberately
+# wrong versions and prove that the GPU tests' shapes and starting parameters
+# react to each.  The default step is what it was, bit for bit.
+def _bn_batch_stats(zz):
+    """per-channel batch mean and biased variance of [B][co][6][7]"""
+    return zz.mean((0, 2, 3)), zz.var((0, 2, 3))
+
+
+def _bn_running_mean(old, mu, momentum):
+    """r <- (1 - m) r + m * batch mean"""
+    return (1 - momentum) * old + momentum * mu
+
+
+def _bn_bwd_sums(dy, xhat):
+    """dbeta, dgamma"""
+    return dy.sum((0, 2, 3)), (dy * xhat).sum((0, 2, 3))
+
+
+def _bn_bwd_scale(gam, inv, nn_):
+    return gam * inv / nn_
+
+
+def _wgrad(dzf, cols):
+    """[B*42][co], [B*42][ci*9] -> dW [co][ci*9]"""
+    return dzf.T @ cols
+
+
 def forward_backward(params, x, pi, z, blocks, hidden, momentum=0.1, bn_eps=1e-5, masks=None, diag=None):
     """train-mode forward + backward of one batch; returns (params with the BN running
     statistics updated, gradients, loss[3]) — float64"""
@@ -138,10 +168,9 @@ def forward_backward(params, x, pi, z, blocks, hidden, momentum=0.1, bn_eps=1e-5
         W = P[c["w"]:c["w"] + co * ci * 9].reshape(co, ci * 9)
         cols = _im2col(inp)
         zz = (cols @ W.T + P[c["b"]:c["b"] + co]).reshape(B, ROWS, COLS, co).transpose(0, 3, 1, 2)
-        mu = zz.mean((0, 2, 3))
-        var = zz.var((0, 2, 3))
+        mu, var = _bn_batch_stats(zz)
         nn_ = B * CELLS
-        P[c["mu"]:c["mu"] + co] = (1 - momentum) * P[c["mu"]:c["mu"] + co] + momentum * mu
+        P[c["mu"]:c["mu"] + co] = _bn_running_mean(P[c["mu"]:c["mu"] + co], mu, momentum)
         P[c["var"]:c["var"] + co] = (1 - momentum) * P[c["var"]:c["var"] + co] + momentum * var * nn_ / (nn_ - 1)
         inv = 1.0 / np.sqrt(var + bn_eps)
         xhat = (zz - mu[None, :, None, None]) * inv[None, :, None, None]
@@ -188,14 +217,13 @@ def forward_backward(params, x, pi, z, blocks, hidden, momentum=0.1, bn_eps=1e-5
         dy = da * cc["m"]
         xhat, inv = cc["xhat"], cc["inv"]
         nn_ = B * CELLS
-        sb = dy.sum((0, 2, 3))
-        sg = (dy * xhat).sum((0, 2, 3))
+        sb, sg = _bn_bwd_sums(dy, xhat)
         G[c["be"]:c["be"] + co] = sb
         G[c["g"]:c["g"] + co] = sg
         gam = P[c["g"]:c["g"] + co]  # gamma is not changed by the forward
-        dz = (gam * inv / nn_)[None, :, None, None] * (nn_ * dy - sb[None, :, None, None] - xhat * sg[None, :, None, None])
+        dz = _bn_bwd_scale(gam, inv, nn_)[None, :, None, None] * (nn_ * dy - sb[None, :, None, None] - xhat * sg[None, :, None, None])
         dzf = dz.transpose(0, 2, 3, 1).reshape(B * CELLS, co)
-        G[c["w"]:c["w"] + co * ci * 9] = (dzf.T @ cc["cols"]).reshape(-1)
+        G[c["w"]:c["w"] + co * ci * 9] = _wgrad(dzf, cc["cols"]).reshape(-1)
         G[c["b"]:c["b"] + co] = dzf.sum(0)
         if not want_dx:
             return None

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from learner_checks import check_grads_same_masks as _check_grads_same_masks   # shared with test_learner_shapes_gpu.py
 
 pytestmark = pytest.mark.gpu
 
@@ -571,32 +572,6 @@ def test_learner_vs_torch_golden(spai):
     check_learner_params(P3, params3, [g_ref], blocks, hidden, 3, tol=1e-4)
     L.close()
     e.close()
-
-
-def _check_grads_same_masks(L, g, p0, batch, blocks):
-    """fp32 device gradient vs the float64 restatement run with the DEVICE's ReLU
-    masks (spai_learner_activation > 0).  BN's beta is 0 at init, so some
-    pre-activations sit within fp32 rounding of 0 and take either side of the kink
-    depending on the summation order; forcing the device's side in the
-    restatement removes those flips, so every entry is held to the bulk bound
-    3e-4 * max|g| (fp32 through 2*blocks+3 layers).  The masks may differ from
-    the restatement's own (pre > 0) only where its pre-activation is within
-    1e-4 of its layer's scale of zero: a flip anywhere else fails."""
-    import learner_ref as LR
-    nl = 2 * blocks + 3
-    masks = [L.activation(l) > 0 for l in range(nl)]
-    diag = {}
-    n = len(p0)
-    _, _, _, _, ref = LR.train_step(p0, np.zeros(n), np.zeros(n), 0, *batch, blocks, 64, masks=masks, diag=diag)
-    flips = 0
-    for l in range(nl):
-        pre = diag["pre"][l]
-        diff = masks[l] != (pre > 0)
-        flips += int(diff.sum())
-        assert np.all(np.abs(pre[diff]) <= 1e-4 * np.abs(pre).max()), (l, np.abs(pre[diff]).max())
-    d, m = np.abs(g - ref), np.abs(ref).max()
-    assert d.max() <= 3e-4 * m, (d.max() / m, flips)
-    return flips
 
 
 @pytest.mark.parametrize("blocks,B,steps", [(2, 48, 2), (6, 128, 1), (2, 128, 1), (0, 5, 1)])

@@ -139,6 +139,37 @@ def test_ttt_learner_vs_restatement(st, blocks, B, steps):
     eng.close()
 
 
+@pytest.mark.parametrize("blocks,B,steps", [(1, 5, 2), (2, 33, 1), (2, 130, 1)])
+def test_ttt_learner_trained_like_vs_restatement(st, blocks, B, steps):
+    """the same check from bf16_ref.trained_like parameters: conv biases, beta and the
+    running mean away from 0, the running variance away from 1, gammas above 1 and
+    below 0, so the running-statistic blend and every factor of k_tl_bn_bwd count
+    (from init_params the old running mean is 0 and drops out of the blend).  The
+    restatement is pinned to PyTorch float64 autograd from such parameters in
+    tests/test_learner_ref_cpu.py.  The bars are the ones above, unchanged."""
+    import bf16_ref as R
+    import ttt_learner_ref as LR
+    from learner_checks import check_momentum_blend_is_tested, start_params
+    eng = st.TTTEngine(num_searches=1, max_trees=1)
+    batches = _device_batches(eng, B, steps, 2000 * blocks + B)
+    p0 = start_params(st.init_params(blocks, blocks + 7), R.c4_layout(blocks, 64, (3, 3, 3, 9)), "trained", 60 + blocks)
+    L = st.TTTLearner(eng, blocks, p0)
+    dev_losses = [L.train_batch(*batches[0])]
+    assert L.last_batch() == B
+    _check_grads_same_masks(L, L.grads(), p0, batches[0], blocks)   # reads the first step's activations
+    dev_losses += [L.train_batch(*b) for b in batches[1:]]
+    P_ref, ref_losses, ref_grads = LR.train(p0, batches, blocks)
+    print("loss", np.array(dev_losses), ref_losses)
+    np.testing.assert_allclose(dev_losses[0], ref_losses[0], rtol=1e-4, atol=1e-5)
+    np.testing.assert_allclose(np.array(dev_losses), ref_losses, rtol=1e-3, atol=1e-4)
+    LR.check_learner_params(L.params(), P_ref, ref_grads, blocks, steps, tol=1e-4)
+    P1_ref = P_ref if steps == 1 else LR.train(p0, batches[:1], blocks)[0]
+    print("running mean vs 0.1 * batch mean / vs old: %.3g / %.3g x the tolerance" % tuple(
+        check_momentum_blend_is_tested(p0, P1_ref, LR._layout(blocks)[0])))
+    L.close()
+    eng.close()
+
+
 def test_ttt_learner_deterministic(st):
     """two learners, the same parameters, the same two batches of 17: bit-identical"""
     blocks = 2
