@@ -233,6 +233,60 @@ typedef struct spai_eval_cache_stats {
 /* totals since the engine was created; waits for the engine's stream */
 int spai_eval_cache_get_stats(spai_engine *eng, spai_eval_cache_stats *out);
 
+/* ------------------------------------------------------------------ match
+ * play() (main.rs:54-135) with a second evaluator in the human's seat, over
+ * n_games games at once: which of two players (a net, or plain MCTS on a stub
+ * evaluator) is the stronger.
+ *   Game g has id game_id_base + g and belongs to pair id / 2; player A moves
+ * first when the id is even, B when it is odd.  Both games of a pair start from
+ * the same opening, so every opening is played once with each colour: ply
+ * k < opening_plies plays the idx-th legal column in ascending order, idx =
+ * min((int)(u * (float)n_legal), n_legal - 1) with u the 23-bit Philox uniform
+ * of (cfg.seed, pair, k) (the uniform of self-play's move draw).
+ *   Every game has one tree per player, both created at the position after the
+ * opening.  The side to move searches its own tree with its own evaluator for
+ * its own num_searches iterations, plays the most-visited root child (ties: the
+ * last, spai_policy_best_action's rule) and re-roots its tree there
+ * (use_subtree: the root keeps N and W).  The opponent's tree follows the move:
+ * re-rooted at that action's child when its root is expanded, otherwise (only
+ * before the second player's first search) a fresh tree at the new position.
+ * A game ends on Won or Tied.  All the A-to-move trees of a ply run as one
+ * search chain and all the B-to-move trees as the other, side by side.
+ *   The engine's own cfg.eval, net and temperature are not used and stay as they
+ * are.  The evaluation cache (above) serves each player only its own evaluations
+ * and the call leaves it empty.  2 * n_games <= cfg.max_trees;
+ * 1 <= num_searches <= cfg.num_searches; opening_plies <= 6 (no game ends before
+ * ply 7): otherwise SPAI_ERR_INVALID.  A NaN UCB or a root without a visited
+ * child (num_searches = 1) is SPAI_ERR_NAN, as in self-play. */
+typedef struct spai_match_player {
+    int32_t eval;            /* spai_eval */
+    uint32_t num_searches;   /* simulations per move */
+    spai_net *net;           /* SPAI_EVAL_NET: the player's net (bf16 or fp32); else ignored */
+} spai_match_player;
+typedef struct spai_match_config {
+    uint32_t struct_size;    /* sizeof(spai_match_config) */
+    uint32_t opening_plies;  /* 0..6 */
+    uint64_t seed;           /* the openings' Philox key */
+} spai_match_config;
+typedef struct spai_match_game {
+    uint64_t game_id;
+    int8_t a_moves_first;
+    int8_t result_a;         /* +1 A won, 0 draw, -1 B won */
+    uint8_t n_moves;         /* plies, the opening's included */
+    uint8_t moves[42];       /* the column of every ply */
+} spai_match_game;
+typedef struct spai_match_stats {
+    double a_wins[2], draws[2], b_wins[2];   /* [0]: games A moved first, [1]: B moved first */
+    double sims[2], evals[2];                /* per player (A, B): trees x iterations, live leaves */
+    double seconds;
+} spai_match_stats;
+/* struct_size set, opening_plies 4, seed 0 */
+int spai_match_config_default(spai_match_config *cfg);
+/* games [n_games] and stats may be NULL.  Every return leaves the engine idle. */
+int spai_match_run(spai_engine *eng, const spai_match_player *a, const spai_match_player *b, uint32_t n_games,
+                   uint64_t game_id_base, const spai_match_config *cfg, spai_match_game *games,
+                   spai_match_stats *stats);
+
 /* ------------------------------------------------------------------ profiling
  * Per-kernel average device time of the last spai_selfplay_run / spai_search
  * call, measured with HIP events on each search chain's stream when enabled.

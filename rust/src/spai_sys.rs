@@ -104,6 +104,44 @@ pub struct spai_adam_config {
 
 pub enum spai_engine {}
 pub enum spai_net {}
+
+// play() (main.rs:54-135) between two evaluators: spai_match_run
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct spai_match_player {
+    pub eval: i32,
+    pub num_searches: u32,
+    pub net: *mut spai_net,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct spai_match_config {
+    pub struct_size: u32,
+    pub opening_plies: u32,
+    pub seed: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct spai_match_game {
+    pub game_id: u64,
+    pub a_moves_first: i8,
+    pub result_a: i8,
+    pub n_moves: u8,
+    pub moves: [u8; 42],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct spai_match_stats {
+    pub a_wins: [f64; 2],
+    pub draws: [f64; 2],
+    pub b_wins: [f64; 2],
+    pub sims: [f64; 2],
+    pub evals: [f64; 2],
+    pub seconds: f64,
+}
 pub enum spai_learner {}
 pub enum spai_ttt {}
 pub enum spai_ttt_net {}
@@ -147,6 +185,10 @@ extern "C" {
                              user: *mut c_void, stats: *mut spai_selfplay_stats) -> c_int;
     pub fn spai_selfplay_stream(e: *mut spai_engine, n_games: u32, window: u32, game_id_base: u64,
                                 sink: spai_sample_sink, user: *mut c_void, stats: *mut spai_selfplay_stats) -> c_int;
+    pub fn spai_match_config_default(cfg: *mut spai_match_config) -> c_int;
+    pub fn spai_match_run(e: *mut spai_engine, a: *const spai_match_player, b: *const spai_match_player, n_games: u32,
+                          game_id_base: u64, cfg: *const spai_match_config, games: *mut spai_match_game,
+                          stats: *mut spai_match_stats) -> c_int;
 
     // TicTacToe (game/tictactoe.rs, model/tictactoe.rs)
     pub fn spai_ttt_create(cfg: *const spai_config, device: c_int, out: *mut *mut spai_ttt) -> c_int;

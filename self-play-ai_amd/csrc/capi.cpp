@@ -391,6 +391,36 @@ int spai_selfplay_stream(spai_engine *e, uint32_t n_games, uint32_t window, uint
     return selfplay_run(e, n_games, gid_base, sink, user, stats, window);
 }
 
+int spai_match_config_default(spai_match_config *cfg) {
+    PTR_CHECK(cfg);
+    *cfg = spai_match_config{};
+    cfg->struct_size = (uint32_t)sizeof(spai_match_config);
+    cfg->opening_plies = 4;
+    cfg->seed = 0;
+    return SPAI_OK;
+}
+
+int spai_match_run(spai_engine *e, const spai_match_player *a, const spai_match_player *b, uint32_t n_games,
+                   uint64_t gid_base, const spai_match_config *cfg, spai_match_game *games, spai_match_stats *stats) {
+    ENG_CHECK(e);
+    PTR_CHECK(a);
+    PTR_CHECK(b);
+    PTR_CHECK(cfg);
+    SPAI_CHECK(cfg->struct_size == sizeof(spai_match_config), SPAI_ERR_INVALID,
+               "spai_match_config.struct_size %u, expected %zu", cfg->struct_size, sizeof(spai_match_config));
+    SPAI_CHECK(cfg->opening_plies <= 6, SPAI_ERR_INVALID, "opening_plies %u > 6", cfg->opening_plies);
+    SPAI_CHECK(n_games > 0 && 2 * (uint64_t)n_games <= e->cfg.max_trees, SPAI_ERR_INVALID,
+               "a match of %u games needs %llu trees, max_trees=%u", n_games, 2ull * n_games, e->cfg.max_trees);
+    for (const spai_match_player *p : {a, b}) {
+        SPAI_CHECK(p->eval >= SPAI_EVAL_NET && p->eval <= SPAI_EVAL_HASH, SPAI_ERR_INVALID, "bad eval kind %d", p->eval);
+        SPAI_CHECK(p->eval != SPAI_EVAL_NET || p->net, SPAI_ERR_INVALID, "player with eval = NET but no net");
+        SPAI_CHECK(p->eval != SPAI_EVAL_NET || p->net->eng == e, SPAI_ERR_INVALID, "net belongs to another engine");
+        SPAI_CHECK(p->num_searches >= 1 && p->num_searches <= e->cfg.num_searches, SPAI_ERR_INVALID,
+                   "player num_searches %u not in [1, cfg.num_searches=%u]", p->num_searches, e->cfg.num_searches);
+    }
+    return match_run(e, a, b, n_games, gid_base, cfg, games, stats);
+}
+
 int spai_engine_set_timing(spai_engine *e, int enabled) {
     ENG_CHECK(e);
     KernelTimer &K = e->timer;

@@ -751,11 +751,14 @@ int cache_clear(spai_engine *e) {
 // kEntriesPerTree per tree slot of max_trees) and allocate the table, on the first search
 // call after a change; on for the net evaluator only.  The counters outlive a resize:
 // the old table's claims are added to the host's total and the device count starts again.
-int cache_prepare(spai_engine *e) {
+// (for_net: a net evaluates in the coming call -- cfg.eval for search and self-play, either
+// player of a match)
+int cache_prepare(spai_engine *e, bool for_net) {
     EvalCache &C = e->cache;
-    if (C.ready) return SPAI_OK;
+    if (C.ready && C.for_net == for_net) return SPAI_OK;
+    C.for_net = for_net;
     uint64_t want = 0;
-    if (e->cfg.eval == SPAI_EVAL_NET) {
+    if (for_net) {
         const char *v = std::getenv("SPAI_EVAL_CACHE");
         if (C.user_set) want = C.requested;
         else if (v) want = std::strtoull(v, nullptr, 10);
@@ -1015,7 +1018,7 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
     hipStream_t st = e->stream;
     // evaluation cache: allocated on first use; emptied here, between search calls
     // (no chain runs), once it is more than 3/4 full, so a long stream keeps hitting
-    SPAI_TRY(cache_prepare(e));
+    SPAI_TRY(cache_prepare(e, kind == SPAI_EVAL_NET));
     if (e->cache.buckets && (uint64_t)e->cache.fill_seen * 4 > e->cache.entries() * 3) SPAI_TRY(cache_clear(e));
     // tail mode (select_tree RUN_ON, one chain): late in a game, when in the previous
     // search call of these trees no tree evaluated SPAI_TAIL_TREE_EVALS leaves or
@@ -1186,6 +1189,23 @@ int search_finish(spai_engine *e, const SearchRun &R, uint32_t num_searches, con
     e->last_max_tree_evals = max_tree_evals;
     return SPAI_OK;
 }
+
+// the device buffer of a move step's records and its two pinned host copies (move
+// m's is read while m + 1 runs), at least n_words each
+int move_buffers(spai_engine *e, size_t n_words) {
+    if (e->h_move_n >= n_words) return SPAI_OK;
+    e->h_move_n = 0;
+    for (uint32_t *&h : e->h_move) {
+        if (h) (void)hipHostFree(h);
+        h = nullptr;
+        void *ph = nullptr;
+        SPAI_HIP(hipHostMalloc(&ph, n_words * 4, hipHostMallocDefault));
+        h = (uint32_t *)ph;
+    }
+    SPAI_TRY(e->move_out.alloc(n_words));
+    e->h_move_n = n_words;
+    return SPAI_OK;
+}
 }  // namespace
 
 int search(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, float *policy,
@@ -1327,20 +1347,8 @@ int selfplay_run(spai_engine *e, uint32_t n_games, uint64_t gid_base, spai_sampl
         e->pow_tab_t = temp;
     }
     // records, then every chain's leaf counters (tail mode: up to ns + kTailChunk + 1)
-    const size_t n_words = 2 + (size_t)W * kMoveRec +
-                           (size_t)spai_engine::kChains * (std::max(ns, 1u) + kTailChunk + 1);
-    if (e->h_move_n < n_words) {
-        e->h_move_n = 0;
-        for (uint32_t *&h : e->h_move) {
-            if (h) (void)hipHostFree(h);
-            h = nullptr;
-            void *ph = nullptr;
-            SPAI_HIP(hipHostMalloc(&ph, n_words * 4, hipHostMallocDefault));
-            h = (uint32_t *)ph;
-        }
-        SPAI_TRY(e->move_out.alloc(n_words));
-        e->h_move_n = n_words;
-    }
+    SPAI_TRY(move_buffers(e, 2 + (size_t)W * kMoveRec +
+                                 (size_t)spai_engine::kChains * (std::max(ns, 1u) + kTailChunk + 1)));
     std::vector<c4::State> h_states((size_t)W * kPlies);   // per tree slot
     std::vector<float> h_pol((size_t)W * kPlies * 7);
     std::vector<int32_t> h_moves((size_t)W * kPlies);
@@ -1544,6 +1552,365 @@ int selfplay_run(spai_engine *e, uint32_t n_games, uint64_t gid_base, spai_sampl
         stats->games = games;
         stats->positions = positions;
         stats->moves = moves;
+        stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+    }
+    return SPAI_OK;
+}
+
+// ---------------------------------------------------------------- match
+// play() (main.rs:54-135) between two evaluators over many games (spai.h "match").
+// Game g of the call owns trees 2g (player A's) and 2g + 1 (B's).  The games run in
+// lockstep, so at every ply the games with A to move and those with B to move are
+// two disjoint tree lists: chain 0 searches A's with A's evaluator, chain 1 B's
+// with B's, side by side like the two halves of a self-play call.  Tail mode (a
+// one-chain schedule) stays off.
+namespace {
+// the opening of pair `pair`: ply k plays the idx-th legal column, idx from one f32 multiply
+__host__ __device__ inline c4::State opening_state(uint64_t seed, uint64_t pair, uint32_t plies, uint8_t *moves) {
+    c4::State s{0, 0, 0, c4::kOngoing};
+    for (uint32_t k = 0; k < plies; ++k) {
+        const uint32_t legal = c4::legal_mask(s.x, s.o, s.status);
+        const int n_legal = (int)c4::popc32(legal);
+        int idx = (int)(sample_u01_f32(seed, pair, k) * (float)n_legal);
+        idx = idx < n_legal - 1 ? idx : n_legal - 1;
+        const int a = c4::kth_bit(legal, idx);
+        c4::State ns = s;
+        (void)c4::next_state(s, a, ns);
+        s = ns;
+        if (moves) moves[k] = (uint8_t)a;
+    }
+    return s;
+}
+
+// both trees of every game: an empty arena whose root is the position after the opening
+__global__ void k_match_start(TreeView T, RootsOut R, uint32_t n_games, uint64_t gid_base, uint64_t seed,
+                              uint32_t plies) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_games) return;
+    const c4::State s = opening_state(seed, (gid_base + g) / 2, plies, nullptr);
+    for (uint32_t t = 2 * g; t < 2 * g + 2; ++t) {
+        T.nodes[(size_t)t * T.cap] = make_uint4(0u, 0u, 0u, kNoChildren);
+        T.next_free[t] = 1;
+        R.root[t] = 0;
+        R.x[t] = s.x;
+        R.o[t] = s.o;
+        R.n[t] = s.n;
+        R.status[t] = s.status;
+    }
+}
+
+// The move after a ply's search call, per searched tree t (the mover's; t ^ 1 is the
+// opponent's tree of the same game, at the same position): the most-visited root
+// child, ties to the last; for a game that goes on, the mover's tree re-rooted at it
+// (use_subtree) and the opponent's at the same action's child -- the same index, its
+// root being the same position -- or, while that root has no children (before the
+// second player's first search), started anew at the new position.  The record per
+// tree and the words around the records are k_advance's; rec[8] without a visited
+// child is kPickNone | 2 (the all-zero code of weighted_index_f32).  Chain h's
+// per-iteration leaf counts follow the records at counts[h * stride ..].
+struct MatchCounts {
+    const uint32_t *p[2];
+    uint32_t n[2];
+};
+__global__ void k_match_advance(TreeView T, RootsOut R, const uint32_t *__restrict__ active, uint32_t n_active,
+                                const uint32_t *err, const uint32_t *cache_fill, MatchCounts cc, uint32_t stride,
+                                uint32_t *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (blockIdx.x == 0) {
+        if (threadIdx.x == 0) {
+            out[0] = *err;
+            out[1] = cache_fill ? *cache_fill : 0u;
+        }
+        uint32_t *counts = out + 2 + (size_t)n_active * kMoveRec;
+        for (int h = 0; h < 2; ++h)
+            for (uint32_t j = threadIdx.x; j < cc.n[h]; j += blockDim.x) counts[(size_t)h * stride + j] = cc.p[h][j];
+    }
+    if (i >= n_active) return;
+    const uint32_t t = active[i], opp = t ^ 1u;
+    uint4 *nodes = T.nodes + (size_t)t * T.cap;
+    const uint4 r = nodes[T.root[t]];
+    const uint32_t nch = r.w == kNoChildren ? 0 : r.w >> 24, first = r.w & 0xFFFFFFu;
+    uint32_t *rec = out + 2 + (size_t)i * kMoveRec;
+    rec[0] = r.w;
+    uint32_t best = 0;
+    int idx = -1;
+    for (uint32_t k = 0; k < (uint32_t)c4::kActions; ++k) {
+        const uint32_t v = k < nch ? nodes[first + k].x : 0u;
+        rec[1 + k] = v;
+        if (k < nch && v >= best) {
+            best = v;
+            idx = (int)k;
+        }
+    }
+    rec[9] = T.evals[t];
+    if (best == 0) {
+        rec[8] = kPickNone | 2u;
+        return;
+    }
+    const c4::State rs{T.root_x[t], T.root_o[t], T.root_n[t], T.root_status[t]};
+    const int a = c4::kth_bit(c4::legal_mask(rs.x, rs.o, rs.status), idx);
+    c4::State cs = rs;
+    (void)c4::next_state(rs, a, cs);
+    rec[8] = (uint32_t)idx | (uint32_t)a << 8 | (uint32_t)cs.status << 16;
+    if (cs.status != c4::kOngoing) return;
+    R.root[t] = first + (uint32_t)idx;
+    uint4 *onodes = T.nodes + (size_t)opp * T.cap;
+    const uint32_t ow = onodes[T.root[opp]].w;
+    if (ow != kNoChildren) {
+        R.root[opp] = (ow & 0xFFFFFFu) + (uint32_t)idx;
+    } else {
+        onodes[0] = make_uint4(0u, 0u, 0u, kNoChildren);
+        T.next_free[opp] = 1;
+        R.root[opp] = 0;
+    }
+    for (uint32_t u = t & ~1u; u < (t & ~1u) + 2; ++u) {
+        R.x[u] = cs.x;
+        R.o[u] = cs.o;
+        R.n[u] = cs.n;
+        R.status[u] = cs.status;
+    }
+}
+
+struct MatchSide {
+    int kind;
+    spai_net *net;
+    uint32_t iters;
+    uint32_t gen;   // its generation in the evaluation cache
+};
+
+// One ply's search call: chain h runs trees[off h .. off h + cnt[h]) (player h's) for
+// side[h].iters iterations with side[h]'s evaluator, up to the join on the engine
+// stream.  A chain without trees launches nothing.  The launches per chain are
+// search_launch's (select; evaluate, expand + select ...; evaluate, expand).
+int match_search_launch(spai_engine *e, const uint32_t *trees, const uint32_t (&cnt)[2], const MatchSide (&side)[2]) {
+    Trees &T = e->trees;
+    hipStream_t st = e->stream;
+    const uint32_t n = cnt[0] + cnt[1];
+    const uint32_t off[2] = {0, cnt[0]};
+    bool cached[2];
+    int nets = 0;   // chains whose forwards share the CUs
+    for (int h = 0; h < 2; ++h) {
+        cached[h] = e->cache.buckets && side[h].kind == SPAI_EVAL_NET;
+        if (!cnt[h]) continue;
+        nets += side[h].kind == SPAI_EVAL_NET;
+        Batch &B = e->batch[h];
+        const uint32_t nc = side[h].iters;
+        if (B.iter_counts.n < nc) SPAI_TRY(B.iter_counts.alloc(nc));
+        SPAI_HIP(hipMemsetAsync(B.iter_counts.p, 0, (size_t)nc * 4, st));
+        if (cached[h]) {
+            if (B.iter_hits.n < nc) SPAI_TRY(B.iter_hits.alloc(nc));
+            SPAI_HIP(hipMemsetAsync(B.iter_hits.p, 0, (size_t)nc * 4, st));
+        }
+    }
+    SPAI_HIP(hipMemcpyAsync(e->active.p, trees, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    SPAI_HIP(hipMemsetAsync(e->err.p, 0, 4, st));
+    SPAI_HIP(hipMemsetAsync(T.evals.p, 0, ((size_t)T.n_trees + 2) * 4, st));
+    if (cnt[1]) {
+        SPAI_HIP(hipEventRecord(e->ev_fork, st));
+        SPAI_HIP(hipStreamWaitEvent(e->chain_stream[1], e->ev_fork, 0));
+    }
+    const TreeView tv = tree_view(e);
+    auto bview = [&](int h, uint32_t it) {
+        BatchView b = batch_view(e, h, it);
+        if (!cached[h]) b.hits = nullptr;
+        return b;
+    };
+    const uint32_t iters = std::max(side[0].iters, side[1].iters);
+    for (uint32_t it = 0; it < iters; ++it) {
+        for (int h = 0; h < 2; ++h) {
+            if (!cnt[h] || it >= side[h].iters) continue;
+            const hipStream_t sh = e->chain_stream[h];
+            const CacheView cv = cached[h] ? CacheView{e->cache.table.p, e->cache.buckets - 1u, side[h].gen, e->cache.ctr.p}
+                                           : CacheView{nullptr, 0u, 0u, nullptr};
+            const BatchView bv = bview(h, it);
+            const uint32_t nh = cnt[h], g8 = (nh + kTreesPerBlock - 1) / kTreesPerBlock;
+            const uint32_t *act = e->active.p + off[h];
+            if (it == 0) k_select<false><<<g8, kBlock, 0, sh>>>(tv, bv, cv, act, nh, e->cfg.c, e->err.p, 0u);
+            if (side[h].kind == SPAI_EVAL_NET) {
+                SPAI_TRY(net_eval_batch(side[h].net, sh, bv.count, nh, bv.mine, bv.theirs, bv.priors, bv.value, 0u,
+                                        std::max(nets, 1)));
+            } else {
+                k_eval_stub<<<(nh + kBlock - 1) / kBlock, kBlock, 0, sh>>>(bv, nh, side[h].kind);
+            }
+            if (it + 1 < side[h].iters)
+                k_expand_select<false><<<g8, kBlock, 0, sh>>>(tv, bv, bview(h, it + 1), cv, act, nh, e->cfg.c,
+                                                              e->err.p, 0u);
+            else
+                k_expand<<<g8, kBlock, 0, sh>>>(tv, bv, cv, nh, e->err.p);
+        }
+    }
+    SPAI_HIP(hipGetLastError());
+    if (cnt[1]) {
+        SPAI_HIP(hipEventRecord(e->ev_join[1], e->chain_stream[1]));
+        SPAI_HIP(hipStreamWaitEvent(st, e->ev_join[1], 0));
+    }
+    return SPAI_OK;
+}
+}  // namespace
+
+int match_run(spai_engine *e, const spai_match_player *a, const spai_match_player *b, uint32_t n_games,
+              uint64_t gid_base, const spai_match_config *cfg, spai_match_game *games, spai_match_stats *stats) {
+    const auto t_start = std::chrono::steady_clock::now();
+    const uint32_t W = 2 * n_games;
+    SPAI_TRY(trees_create(e, W));
+    Trees &T = e->trees;
+    EvalCache &C = e->cache;
+    hipStream_t st = e->stream;
+    MatchSide side[2] = {{a->eval, a->net, a->num_searches, 0u}, {b->eval, b->net, b->num_searches, 0u}};
+    const uint32_t stride = std::max(side[0].iters, side[1].iters);
+    SPAI_TRY(move_buffers(e, 2 + (size_t)W * kMoveRec + 2 * (size_t)stride));
+    // Every return, errors included, leaves the streams idle (the next ply may be in
+    // flight when a check fails), the cache without the match's entries and the trees
+    // as trees_create leaves them (the host mirrors of the roots are not kept in a match).
+    struct Finish {
+        spai_engine *e;
+        uint32_t w;
+        ~Finish() {
+            (void)hipStreamSynchronize(e->stream);
+            for (hipStream_t cs : e->chain_stream)
+                if (cs) (void)hipStreamSynchronize(cs);
+            (void)cache_clear(e);
+            (void)trees_create(e, w);
+        }
+    } finish{e, W};
+    // The evaluation cache, on when a net plays: each player's entries carry a
+    // generation of their own, so neither is ever served the other's evaluations
+    // (one generation when both play the same net).  The table is emptied before the
+    // generations are drawn, so no older entry can carry either.
+    SPAI_TRY(cache_prepare(e, side[0].kind == SPAI_EVAL_NET || side[1].kind == SPAI_EVAL_NET));
+    const bool same_net = side[0].kind == SPAI_EVAL_NET && side[1].kind == SPAI_EVAL_NET && side[0].net == side[1].net;
+    auto new_gens = [&]() -> int {
+        SPAI_TRY(cache_clear(e));
+        side[0].gen = C.gen;
+        if (!same_net) C.gen = C.gen % 32767u + 1u;
+        side[1].gen = C.gen;
+        return SPAI_OK;
+    };
+    if (C.buckets) SPAI_TRY(new_gens());
+    const TreeView tv = tree_view(e);
+    const RootsOut ro{T.root.p, T.root_x.p, T.root_o.p, T.root_n.p, T.root_status.p};
+    k_match_start<<<(n_games + 255) / 256, 256, 0, st>>>(tv, ro, n_games, gid_base, cfg->seed, cfg->opening_plies);
+    SPAI_HIP(hipGetLastError());
+    // the host's record of every game: position, moves, outcome
+    std::vector<c4::State> pos(n_games);
+    std::vector<spai_match_game> rec_games(n_games);
+    for (uint32_t g = 0; g < n_games; ++g) {
+        spai_match_game &G = rec_games[g];
+        G = spai_match_game{};
+        G.game_id = gid_base + g;
+        G.a_moves_first = (int8_t)(((gid_base + g) & 1ull) == 0);
+        G.n_moves = (uint8_t)cfg->opening_plies;
+        pos[g] = opening_state(cfg->seed, (gid_base + g) / 2, cfg->opening_plies, G.moves);
+    }
+    // a ply's trees: player A's of the live games where A is to move, then B's of the others
+    struct Ply {
+        std::vector<uint32_t> trees;
+        uint32_t cnt[2] = {0, 0};
+    } ply[2];
+    auto build = [&](const std::vector<uint32_t> &live_games, uint32_t ply_no, Ply &P) {
+        P.trees.clear();
+        for (uint32_t p = 0; p < 2; ++p) {
+            for (uint32_t g : live_games)
+                if ((((gid_base + g) ^ ply_no) & 1ull) == p) P.trees.push_back(2 * g + p);
+            P.cnt[p] = (uint32_t)P.trees.size() - (p ? P.cnt[0] : 0u);
+        }
+    };
+    auto launch = [&](const Ply &P, uint32_t *dst) -> int {
+        if (C.buckets && (uint64_t)C.fill_seen * 4 > C.entries() * 3) SPAI_TRY(new_gens());
+        SPAI_TRY(match_search_launch(e, P.trees.data(), P.cnt, side));
+        const uint32_t na = (uint32_t)P.trees.size();
+        MatchCounts cc{};
+        for (int h = 0; h < 2; ++h) {
+            cc.p[h] = e->batch[h].iter_counts.p;
+            cc.n[h] = P.cnt[h] ? side[h].iters : 0u;
+        }
+        k_match_advance<<<(na + 63) / 64, 64, 0, st>>>(tv, ro, e->active.p, na, e->err.p,
+                                                       C.buckets ? C.ctr.p : nullptr, cc, stride, e->move_out.p);
+        SPAI_HIP(hipGetLastError());
+        const size_t words = 2 + (size_t)na * kMoveRec + 2 * (size_t)stride;
+        SPAI_HIP(hipMemcpyAsync(dst, e->move_out.p, words * 4, hipMemcpyDeviceToHost, st));
+        return SPAI_OK;
+    };
+    std::vector<uint32_t> live_games(n_games), next_games;
+    for (uint32_t g = 0; g < n_games; ++g) live_games[g] = g;
+    std::vector<uint8_t> ended(n_games, 0);
+    double sims[2] = {0, 0}, evals[2] = {0, 0};
+    uint32_t ply_no = cfg->opening_plies;
+    int cur = 0;
+    build(live_games, ply_no, ply[0]);
+    SPAI_TRY(launch(ply[0], e->h_move[0]));
+    while (!live_games.empty()) {
+        const Ply &P = ply[cur];
+        const uint32_t na = (uint32_t)P.trees.size();
+        const uint32_t *mo = e->h_move[cur];
+        SPAI_HIP(hipStreamSynchronize(st));
+        const uint32_t err = mo[0];
+        SPAI_CHECK(!(err & kErrCapacity), SPAI_ERR_CAPACITY, "node arena full (cap %u per tree)", T.cap);
+        SPAI_CHECK(!(err & kErrDepth), SPAI_ERR_CAPACITY, "tree deeper than %d", kMaxDepth);
+        SPAI_CHECK(!(err & kErrNan), SPAI_ERR_NAN, "NaN UCB in select (reference: partial_cmp().unwrap() panics)");
+        const uint32_t *counts = mo + 2 + (size_t)na * kMoveRec;
+        bool stop = false;
+        for (uint32_t p = 0, i = 0; p < 2; ++p) {
+            if (!P.cnt[p]) continue;
+            double served = 0, fwd = 0;
+            for (uint32_t k = 0; k < P.cnt[p]; ++k, ++i) {
+                const uint32_t *rec = mo + 2 + (size_t)i * kMoveRec;
+                served += rec[9];
+                stop |= (rec[8] & kPickNone) != 0;
+                ended[P.trees[i] / 2] = ((rec[8] >> 16) & 0xFFu) != c4::kOngoing;
+            }
+            for (uint32_t j = 0; j < side[p].iters; ++j) fwd += counts[(size_t)p * stride + j];
+            sims[p] += (double)P.cnt[p] * side[p].iters;
+            evals[p] += served;
+            if (C.buckets && side[p].kind == SPAI_EVAL_NET) {
+                C.lookups += served;
+                C.hits += served - fwd;
+            }
+        }
+        if (C.buckets) C.fill_seen = mo[1];
+        SPAI_CHECK(!stop, SPAI_ERR_NAN, "no visited root child to play (num_searches = 1 visits none)");
+        // the games that go on, in order, search their next ply while the host records this one
+        next_games.clear();
+        for (uint32_t g : live_games)
+            if (!ended[g]) next_games.push_back(g);
+        if (!next_games.empty()) {
+            build(next_games, ply_no + 1, ply[cur ^ 1]);
+            SPAI_TRY(launch(ply[cur ^ 1], e->h_move[cur ^ 1]));
+        }
+        for (uint32_t i = 0; i < na; ++i) {
+            const uint32_t t = P.trees[i], g = t / 2, p = t & 1u;
+            const uint32_t *rec = mo + 2 + (size_t)i * kMoveRec;
+            const uint32_t w = rec[0], pick = rec[8];
+            const uint32_t nch = w == kNoChildren ? 0 : w >> 24;
+            const c4::State rs = pos[g];
+            const uint32_t legal = c4::legal_mask(rs.x, rs.o, rs.status);
+            const int idx = (int)(pick & 0xFFu), mv = (int)((pick >> 8) & 0xFFu);
+            c4::State cs;
+            SPAI_CHECK((uint32_t)idx < nch && nch == c4::popc32(legal) && mv == c4::kth_bit(legal, idx) &&
+                           c4::next_state(rs, mv, cs) == 0 && cs.status == ((pick >> 16) & 0xFFu),
+                       SPAI_ERR_INVALID, "internal: game %u's device move does not replay", g);
+            spai_match_game &G = rec_games[g];
+            SPAI_CHECK(G.n_moves < c4::kCells, SPAI_ERR_INVALID, "internal: game %u longer than 42 plies", g);
+            G.moves[G.n_moves++] = (uint8_t)mv;
+            pos[g] = cs;
+            if (cs.status == c4::kWon) G.result_a = p == 0 ? 1 : -1;
+        }
+        live_games.swap(next_games);
+        cur ^= 1;
+        ++ply_no;
+    }
+    if (games)
+        for (uint32_t g = 0; g < n_games; ++g) games[g] = rec_games[g];
+    if (stats) {
+        *stats = spai_match_stats{};
+        for (const spai_match_game &G : rec_games) {
+            const int f = G.a_moves_first ? 0 : 1;
+            (G.result_a > 0 ? stats->a_wins : G.result_a < 0 ? stats->b_wins : stats->draws)[f] += 1;
+        }
+        for (int p = 0; p < 2; ++p) {
+            stats->sims[p] = sims[p];
+            stats->evals[p] = evals[p];
+        }
         stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     }
     return SPAI_OK;

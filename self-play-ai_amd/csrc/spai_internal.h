@@ -119,6 +119,7 @@ struct EvalCache {
     bool user_set = false;          // capacity set through spai_eval_cache_set_capacity (else SPAI_EVAL_CACHE / default)
     uint64_t requested = 0;         // user_set: entries asked for (0: off)
     bool ready = false;             // capacity resolved and the table allocated (or the cache off)
+    bool for_net = false;           // ... for a call whose evaluator is a net (a stub's call keeps it off)
     uint32_t buckets = 0;           // power of two; 0: off
     uint32_t gen = 0;               // weight/epoch generation in the key words' spare bits, 1..32767
     DevBuf<uint4> table;            // [buckets][kWays][4]
@@ -339,6 +340,8 @@ int selfplay_run(spai_engine *e, uint32_t n_games, uint64_t gid_base, spai_sampl
 int eval_cache_set_capacity(spai_engine *e, uint64_t entries);
 int eval_cache_clear(spai_engine *e);
 int eval_cache_stats(spai_engine *e, spai_eval_cache_stats *out);
+int match_run(spai_engine *e, const spai_match_player *a, const spai_match_player *b, uint32_t n_games,
+              uint64_t gid_base, const spai_match_config *cfg, spai_match_game *games, spai_match_stats *stats);
 
 inline c4::State from_abi(const spai_c4_state &s) { return c4::State{s.x, s.o, s.num_actions_played, s.status}; }
 inline spai_c4_state to_abi(const c4::State &s) {

@@ -33,6 +33,7 @@ SYMBOLS = [
     "spai_net_destroy", "spai_net_forward", "spai_predict", "spai_engine_set_net", "spai_trees_create",
     "spai_tree_reset", "spai_search", "spai_tree_use_subtree", "spai_tree_node", "spai_tree_size",
     "spai_selfplay_run", "spai_selfplay_stream", "spai_eval_cache_set_capacity", "spai_eval_cache_get_stats",
+    "spai_match_config_default", "spai_match_run",
     "spai_engine_set_timing", "spai_engine_timing", "spai_engine_timing_items",
     "spai_net_phase_cycles", "spai_net_bench", "spai_net_bench_conc", "spai_adam_config_default", "spai_learner_create", "spai_learner_destroy",
     "spai_learner_train_batch", "spai_learner_train_batches", "spai_learner_params", "spai_learner_grads", "spai_learner_activation", "spai_comm_unique_id",
@@ -85,6 +86,24 @@ class SelfPlayStats(C.Structure):
 
 class EvalCacheStats(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("lookups", "hits", "inserts", "dropped", "clears", "capacity")]
+
+
+class MatchPlayer(C.Structure):
+    _fields_ = [("eval", C.c_int32), ("num_searches", C.c_uint32), ("net", C.c_void_p)]
+
+
+class MatchConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("opening_plies", C.c_uint32), ("seed", C.c_uint64)]
+
+
+class MatchGame(C.Structure):
+    _fields_ = [("game_id", C.c_uint64), ("a_moves_first", C.c_int8), ("result_a", C.c_int8),
+                ("n_moves", C.c_uint8), ("moves", C.c_uint8 * 42)]
+
+
+class MatchStats(C.Structure):
+    _fields_ = [(k, C.c_double * 2) for k in ("a_wins", "draws", "b_wins", "sims", "evals")] + \
+               [("seconds", C.c_double)]
 
 
 class AdamConfig(C.Structure):
@@ -172,6 +191,9 @@ def lib():
         L.spai_selfplay_stream.argtypes = [vp, u32, u32, u64, SINK, vp, P(SelfPlayStats)]
         L.spai_eval_cache_set_capacity.argtypes = [vp, u64]
         L.spai_eval_cache_get_stats.argtypes = [vp, P(EvalCacheStats)]
+        L.spai_match_config_default.argtypes = [P(MatchConfig)]
+        L.spai_match_run.argtypes = [vp, P(MatchPlayer), P(MatchPlayer), u32, u64, P(MatchConfig), P(MatchGame),
+                                     P(MatchStats)]
         L.spai_engine_set_timing.argtypes = [vp, i32]
         L.spai_engine_timing.argtypes = [vp, vp, vp]
         L.spai_engine_timing_items.argtypes = [vp, vp, vp]
@@ -441,6 +463,33 @@ class Engine:
         else:
             _check(lib().spai_selfplay_stream(self.h, n_games, window, game_id_base, cb, None, C.byref(st)))
         return games, {k: getattr(st, k) for k, _ in SelfPlayStats._fields_}
+
+    # ---- match
+    def match(self, a, b, n_games, opening_plies=None, seed=0, game_id_base=0):
+        """play() (main.rs:54-135) between two players over n_games games (spai_match_run).
+        A player is (eval_kind, net, num_searches); net is a Net for EVAL_NET, else
+        ignored (None).  Game i has id game_id_base + i; A moves first in the even ids,
+        and both games of a pair (id // 2) share their opening of opening_plies plies
+        (default: spai_match_config_default's).  Returns (games, stats): per game a
+        dict (game, a_moves_first, result_a = +1 A won / 0 draw / -1 B won, moves), and
+        the counts split by who moved first ([0]: A), per-player sims and evals, seconds."""
+        cfg = MatchConfig()
+        _check(lib().spai_match_config_default(C.byref(cfg)))
+        if opening_plies is not None:
+            cfg.opening_plies = opening_plies
+        cfg.seed = seed
+        pl = []
+        for kind, net, sims in (a, b):
+            pl.append(MatchPlayer(int(kind), int(sims), net.h if net is not None else None))
+        out = (MatchGame * max(n_games, 1))()
+        st = MatchStats()
+        _check(lib().spai_match_run(self.h, C.byref(pl[0]), C.byref(pl[1]), n_games, game_id_base, C.byref(cfg), out,
+                                    C.byref(st)))
+        games = [dict(game=int(g.game_id), a_moves_first=bool(g.a_moves_first), result_a=int(g.result_a),
+                      moves=[int(m) for m in g.moves[:g.n_moves]]) for g in out[:n_games]]
+        stats = {k: [float(v) for v in getattr(st, k)] for k in ("a_wins", "draws", "b_wins", "sims", "evals")}
+        stats["seconds"] = float(st.seconds)
+        return games, stats
 
     # ---- evaluation cache (EVAL_NET: positions the net has seen under the current weights)
     def set_eval_cache(self, entries):
