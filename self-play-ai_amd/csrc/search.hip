@@ -1,5 +1,7 @@
-// search.hip — device-resident MCTS (mcts.rs) + the self-play driver
-// (learner_concurrent.rs:169-242).
+// search.hip — device-resident MCTS (mcts.rs): the tree kernels, the evaluation
+// cache, the chain and tail-mode policies, the chain launcher (also self-play's,
+// selfplay.hip, and a match's, match.hip; shared declarations: search_internal.h)
+// and a call's bookkeeping, spai_search and the tree API.
 //
 // Trees live in HBM as per-tree arenas of 16-B node records (spai_internal.h).
 // One search iteration (mcts.rs:214-285) is two launches per search chain:
@@ -21,16 +23,12 @@
 // Leaf batches are double-buffered by iteration parity, and every iteration
 // has its own slot counter (zeroed once per search call).
 // The host only sees the trees between moves: root visit counts come back once
-// per search call.  In self-play the move is sampled on the device too
-// (k_advance), which writes the sampled child as the new root.
+// per search call, or the record of a move step that ran on the device.
 #include <algorithm>
-#include <chrono>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
-#include "philox.h"
-#include "spai_internal.h"
+#include "search_internal.h"
 
 namespace spai {
 namespace {
@@ -42,35 +40,6 @@ constexpr int kLanesPerTree = 8;
 constexpr int kBlock = SPAI_TREE_BLOCK;   // threads per tree-kernel workgroup (kBlock / 8 trees)
 constexpr int kTreesPerBlock = kBlock / kLanesPerTree;
 constexpr uint32_t kErrNan = 1u, kErrCapacity = 2u, kErrDepth = 4u;
-
-struct TreeView {
-    uint4 *nodes;
-    uint32_t cap;
-    const uint32_t *root;
-    uint32_t *next_free;
-    const uint64_t *root_x, *root_o;
-    const uint8_t *root_n, *root_status;
-    uint32_t *path;
-    uint8_t *depth;
-    uint32_t *slot;   // the tree's leaf slot in the current batch, kNoSlot if terminal
-    uint32_t *left;   // tail run-on mode: search iterations the tree still has to run
-    uint32_t *evals;  // live leaves of this search call (the tail-mode policy's input)
-};
-constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
-
-// a hit of the evaluation cache: the tree's slot is in the batch's hit region (marked in T.slot)
-constexpr uint32_t kHitSlot = 0x80000000u;
-
-struct BatchView {
-    uint32_t *count;
-    uint32_t *more;   // tail mode: set when a tree stopped at the run cap with iterations left (else null)
-    uint32_t *tree;
-    uint64_t *mine, *theirs;
-    float *priors;
-    float *value;
-    uint32_t *hits;   // evaluation cache: leaves served from it, in slots cap - 1 downwards (null: cache off)
-    uint32_t cap;
-};
 
 // ---------------------------------------------------------------- evaluation cache
 // A hash table in HBM from a leaf's full position (mine, theirs) to what the
@@ -96,12 +65,6 @@ struct BatchView {
 // words equal its own (full position and generation): then it holds exactly
 // the bytes one forward wrote for exactly this position.  Anything less reads
 // as a miss, and the leaf goes through the forward as before.
-struct CacheView {
-    uint4 *tab;      // null: off
-    uint32_t mask;   // buckets - 1
-    uint32_t gen;
-    uint32_t *ctr;   // [0] entries claimed since the clear, [1] dropped inserts
-};
 constexpr uint32_t kPriorMark = 0x80000000u;
 constexpr int kGenShift = 49;
 
@@ -602,111 +565,11 @@ __global__ void k_root_stats(TreeView T, const uint32_t *__restrict__ active, ui
     for (uint32_t k = 0; k < 7; ++k) out[i * 8 + 1 + k] = k < nch ? nodes[first + k].x : 0u;
 }
 
-// Self-play's move after a search call (learner_concurrent.rs:177-203), per active
-// tree: the root's visit counts, the sampled child (the Philox uniform of philox.h
-// and rand's WeightedIndex<f32> over (visits as f32).powf(T), the weights from a
-// table of the host's powf, so the pick is the host sampler's bit for bit), and for a game that goes on the
-// child written as the tree's new root (use_subtree).  One record per tree goes
-// back to the host: [0] the root's children word, [1..7] the child visit counts,
-// [8] the pick (index | action << 8 | new status << 16; without one, bit 31 and
-// the weighted_index code, or kPickNoTable for a visit count beyond the table),
-// [9] the tree's live leaves of the call.  out[0] gets the error flags, out[1] the
-// evaluation cache's fill, and
-// block 0 copies every chain's per-iteration leaf counts after the records, so
-// one copy brings back everything the host needs.
-constexpr int kMoveRec = 10;
-constexpr uint32_t kPickNone = 0x80000000u, kPickNoTable = 3u;
-struct RootsOut {
-    uint32_t *root;
-    uint64_t *x, *o;
-    uint8_t *n, *status;
-};
-struct ChainCounts {
-    const uint32_t *p[spai_engine::kChains];
-};
-__global__ void k_advance(TreeView T, RootsOut R, const uint32_t *__restrict__ active, uint32_t n_active,
-                          const float *__restrict__ pow_tab, uint32_t pow_n, uint64_t seed,
-                          const uint64_t *__restrict__ slot_gid, uint32_t *__restrict__ slot_move,
-                          const uint32_t *err, const uint32_t *cache_fill, ChainCounts cc, int nchain,
-                          uint32_t n_counts, uint32_t *out) {
+__global__ void k_trees_init(TreeView T, RootsOut R, uint32_t first_tree, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (blockIdx.x == 0) {
-        if (threadIdx.x == 0) {
-            out[0] = *err;
-            out[1] = cache_fill ? *cache_fill : 0u;
-        }
-        uint32_t *counts = out + 2 + (size_t)n_active * kMoveRec;
-        for (int h = 0; h < nchain; ++h)
-            for (uint32_t j = threadIdx.x; j < n_counts; j += blockDim.x) counts[(size_t)h * n_counts + j] = cc.p[h][j];
-    }
-    if (i >= n_active) return;
-    const uint32_t t = active[i];
-    const uint4 *nodes = T.nodes + (size_t)t * T.cap;
-    const uint4 r = nodes[T.root[t]];
-    const uint32_t nch = r.w == kNoChildren ? 0 : r.w >> 24, first = r.w & 0xFFFFFFu;
-    uint32_t vis[c4::kActions];
-#pragma unroll
-    for (int k = 0; k < c4::kActions; ++k) vis[k] = (uint32_t)k < nch ? nodes[first + k].x : 0u;
-    uint32_t *rec = out + 2 + (size_t)i * kMoveRec;
-    rec[0] = r.w;
-#pragma unroll
-    for (int k = 0; k < c4::kActions; ++k) rec[1 + k] = vis[k];
-    rec[9] = T.evals[t];
-    bool beyond = false;
-    int idx = -1;   // weighted_index_with: -1 without children
-    if (nch > 0) {   // WeightedIndex<f32> over (visits as f32).powf(T) (learner_concurrent.rs:189-193)
-        float w[c4::kActions];
-        for (uint32_t k = 0; k < nch; ++k) {
-            beyond |= vis[k] >= pow_n;
-            w[k] = pow_tab[min(vis[k], pow_n - 1)];
-        }
-        idx = weighted_index_f32(w, (int)nch, sample_u01_f32(seed, slot_gid[t], slot_move[t]));
-    }
-    if (beyond || idx < 0) {
-        rec[8] = kPickNone | (beyond ? kPickNoTable : (uint32_t)(-idx));
-        return;
-    }
-    const c4::State rs{T.root_x[t], T.root_o[t], T.root_n[t], T.root_status[t]};
-    const int a = c4::kth_bit(c4::legal_mask(rs.x, rs.o, rs.status), idx);
-    c4::State cs = rs;
-    (void)c4::next_state(rs, a, cs);
-    rec[8] = (uint32_t)idx | (uint32_t)a << 8 | (uint32_t)cs.status << 16;
-    slot_move[t] += 1;   // the game's next move number (its sampling counter)
-    if (cs.status == c4::kOngoing) {
-        R.root[t] = first + (uint32_t)idx;
-        R.x[t] = cs.x;
-        R.o[t] = cs.o;
-        R.n[t] = cs.n;
-        R.status[t] = cs.status;
-    }
+    if (i < n) tree_clear(T, R, first_tree + i);
 }
-// self-play: tree slot list[i] starts game list[n + i] (refill) or game gid_base +
-// slot (list == null, every slot in [0, n)): an empty board as its root, an empty
-// arena, move number 0
-__global__ void k_slots_start(TreeView T, RootsOut R, uint64_t *__restrict__ slot_gid,
-                              uint32_t *__restrict__ slot_move, const uint32_t *__restrict__ list, uint32_t n,
-                              uint64_t gid_base) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t t = list ? list[i] : i;
-    T.nodes[(size_t)t * T.cap] = make_uint4(0u, 0u, 0u, kNoChildren);
-    T.next_free[t] = 1;
-    R.root[t] = 0;
-    R.x[t] = 0;
-    R.o[t] = 0;
-    R.n[t] = 0;
-    R.status[t] = c4::kOngoing;
-    slot_gid[t] = gid_base + (list ? list[n + i] : i);
-    slot_move[t] = 0;
-}
-
-__global__ void k_trees_init(TreeView T, uint32_t first_tree, uint32_t n) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t t = first_tree + i;
-    T.nodes[(size_t)t * T.cap] = make_uint4(0u, 0u, 0u, kNoChildren);
-    T.next_free[t] = 1;
-}
+}  // namespace
 
 TreeView tree_view(spai_engine *e) {
     Trees &T = e->trees;
@@ -715,12 +578,13 @@ TreeView tree_view(spai_engine *e) {
 }
 
 // chain `chain`'s leaf batch of search iteration `it`: buffers by parity, counter per iteration
-BatchView batch_view(spai_engine *e, int chain, uint32_t it) {
+// (cached: the chain looks its leaves up in the evaluation cache)
+static BatchView batch_view(spai_engine *e, int chain, uint32_t it, bool cached) {
     Batch &B = e->batch[chain];
     const size_t h = (size_t)(it & 1u) * B.cap;
     return BatchView{B.iter_counts.p + it, B.iter_more.p ? B.iter_more.p + it : nullptr, B.tree.p + h, B.mine.p + h, B.theirs.p + h,
                      B.priors.p + h * kPriorStride, B.value.p + h,
-                     e->cache.buckets && B.iter_hits.p ? B.iter_hits.p + it : nullptr, B.cap};
+                     cached ? B.iter_hits.p + it : nullptr, B.cap};
 }
 
 CacheView cache_view(spai_engine *e) {
@@ -796,11 +660,7 @@ int cache_prepare(spai_engine *e, bool for_net) {
                 SPAI_HIP(hipMemsetAsync(C.ctr.p, 0, 8, e->stream));
             }
             C.buckets = buckets;
-            SPAI_HIP(hipMemsetAsync(C.ctr.p, 0, 4, e->stream));
-            SPAI_HIP(hipMemsetAsync(C.table.p, 0, C.table.n * sizeof(uint4), e->stream));
-            C.gen = C.gen % 32767u + 1u;
-            C.fill_seen = 0;
-            C.clears += 1;
+            SPAI_TRY(cache_clear(e));   // (the claim counter is zero: nothing added to the host's total)
         }
     }
     C.ready = true;
@@ -825,7 +685,6 @@ constexpr double kMinChainLeaves = 64;
 // still evaluate most iterations -- it took 114 and 49 ms against ~25 and ~18 ms
 // for one launch pair per iteration: profiles/r04/tail.)
 constexpr double kTailLeaves = 0.05;
-constexpr uint32_t kTailChunk = 4;
 constexpr uint32_t kTailTreeEvals = 160;
 constexpr uint32_t kTailRun = 128;   // terminal descents per tree and pass
 static int env_int(const char *name, int dflt) {
@@ -841,7 +700,7 @@ struct ChainPolicy {
     int chains;
     uint32_t grid_cap;   // 0: no cap
 };
-ChainPolicy chains_for(uint32_t n, double last_evals_per_iter) {
+static ChainPolicy chains_for(uint32_t n, double last_evals_per_iter) {
     static const int forced = std::max(0, std::min(spai_engine::kChains, env_int("SPAI_CHAINS", 0)));
     static const int mid_leaves = env_int("SPAI_MID_LEAVES", 0);
     static const int mid_chains = std::max(1, std::min(spai_engine::kChains, env_int("SPAI_MID_CHAINS", 2)));
@@ -859,7 +718,7 @@ ChainPolicy chains_for(uint32_t n, double last_evals_per_iter) {
 }
 
 // upload host root bookkeeping for trees [t0, t0+n)
-int upload_roots(spai_engine *e, uint32_t t0, uint32_t n) {
+static int upload_roots(spai_engine *e, uint32_t t0, uint32_t n) {
     Trees &T = e->trees;
     std::vector<uint64_t> x(n), o(n);
     std::vector<uint8_t> nn(n), st(n);
@@ -880,7 +739,7 @@ int upload_roots(spai_engine *e, uint32_t t0, uint32_t n) {
     return SPAI_OK;
 }
 
-int timer_record(spai_engine *e, int which, uint32_t iter, bool begin, hipStream_t st, int chain) {
+static int timer_record(spai_engine *e, int which, uint32_t iter, bool begin, hipStream_t st, int chain) {
     KernelTimer &K = e->timer;
     if (!K.enabled) return SPAI_OK;
     if (begin) {
@@ -903,9 +762,8 @@ int timer_record(spai_engine *e, int which, uint32_t iter, bool begin, hipStream
 }
 
 // fold the sampled event pairs of one search call into the totals
-// ch_counts [chain][num_searches] leaves per iteration; n_active[chain] trees
-int timer_collect(spai_engine *e, const uint32_t *ch_counts, uint32_t num_searches,
-                  const uint32_t *n_active) {
+// ch_counts [chain][num_searches] leaves per iteration
+static int timer_collect(spai_engine *e, const uint32_t *ch_counts, uint32_t num_searches, const Chain *chains) {
     KernelTimer &K = e->timer;
     if (!K.enabled) return SPAI_OK;
     for (size_t i = 0; i < K.which.size(); ++i) {
@@ -914,7 +772,7 @@ int timer_collect(spai_engine *e, const uint32_t *ch_counts, uint32_t num_search
         const int w = K.which[i], h = K.chain[i];
         K.total_ms[w] += ms;
         K.launches[w] += 1;
-        K.items[w] += w == 0 ? n_active[h] : ch_counts[(size_t)h * num_searches + K.iter[i]];
+        K.items[w] += w == 0 ? chains[h].cnt : ch_counts[(size_t)h * num_searches + K.iter[i]];
     }
     K.used = 0;
     K.which.clear();
@@ -922,8 +780,6 @@ int timer_collect(spai_engine *e, const uint32_t *ch_counts, uint32_t num_search
     K.chain.clear();
     return SPAI_OK;
 }
-
-}  // namespace
 
 int trees_create(spai_engine *e, uint32_t n) {
     SPAI_CHECK(n > 0 && n <= e->cfg.max_trees, SPAI_ERR_INVALID, "trees_create: n=%u exceeds max_trees=%u", n,
@@ -970,7 +826,7 @@ int trees_create(spai_engine *e, uint32_t n) {
     T.h_root_state.assign(n, c4::State{0, 0, 0, c4::kOngoing});
     T.h_root_first.assign(n, 0);
     T.h_root_nch.assign(n, 0);
-    k_trees_init<<<(n + 255) / 256, 256, 0, e->stream>>>(tree_view(e), 0, n);
+    k_trees_init<<<(n + 255) / 256, 256, 0, e->stream>>>(tree_view(e), roots_out(e), 0, n);
     SPAI_HIP(hipGetLastError());
     return upload_roots(e, 0, n);
 }
@@ -988,38 +844,108 @@ int tree_reset(spai_engine *e, uint32_t t, const spai_c4_state *root) {
     T.h_root_state[t] = s;
     T.h_root_first[t] = 0;
     T.h_root_nch[t] = 0;
-    k_trees_init<<<1, 64, 0, e->stream>>>(tree_view(e), t, 1);
+    k_trees_init<<<1, 64, 0, e->stream>>>(tree_view(e), roots_out(e), t, 1);
     SPAI_HIP(hipGetLastError());
     return upload_roots(e, t, 1);
 }
 
-namespace {
-// Policy::normalize: ndarray sum (sequential for 7) then divide
-inline void normalize_policy(const float (&pol)[c4::kActions], float *out) {
-    float s = 0.0f;
-    for (int a = 0; a < c4::kActions; ++a) s = s + pol[a];
-    for (int a = 0; a < c4::kActions; ++a) out[a] = pol[a] / s;
+// the chain's evaluator over batch bv on stream st: the net's forward, or a stub
+static int evaluate(const Chain &c, hipStream_t st, const BatchView &bv, uint32_t grid_cap, int conc) {
+    if (c.kind == SPAI_EVAL_NET)
+        return net_eval_batch(c.net, st, bv.count, c.cnt, bv.mine, bv.theirs, bv.priors, bv.value, grid_cap, conc);
+    k_eval_stub<<<(c.cnt + kBlock - 1) / kBlock, kBlock, 0, st>>>(bv, c.cnt, c.kind);
+    return SPAI_OK;
 }
 
-// one search call's launch layout, for search_finish
-struct SearchRun {
-    int nchain = 1;
-    bool tail = false;
-    uint32_t n_counts = 0;                                  // per-iteration leaf counters per chain
-    uint32_t cnt[spai_engine::kChains] = {0, 0, 0, 0};      // trees per chain
-};
+// Enqueue one search call of `nchain` chains over `trees`, up to the join on the
+// engine stream.  Per chain: select(0); then per iteration: evaluate(it),
+// expand(it)+select(it+1) fused, and expand alone after the last evaluation.  A
+// chain without trees launches nothing and is neither forked nor joined; one with
+// fewer iterations than another stops early.  timed: the engine's timers, when on,
+// sample every stride-th iteration: kind 0 the select-bearing launch (k_select /
+// k_expand_select), 1 the evaluator, 2 the last k_expand.  tail: only the setup,
+// with the counters of the tail passes, which the caller runs.
+int chains_launch(spai_engine *e, const uint32_t *trees, const Chain *chains, int nchain, uint32_t grid_cap, bool timed,
+                  bool tail) {
+    hipStream_t st = e->stream;
+    uint32_t n = 0, iters = 0;
+    int conc = 0;   // chains whose forwards share the CUs
+    for (int h = 0; h < nchain; ++h) {   // per-iteration leaf counters (also the batch slot counters)
+        const Chain &c = chains[h];
+        if (!c.cnt) continue;
+        n += c.cnt;
+        iters = std::max(iters, c.iters);
+        conc += c.kind == SPAI_EVAL_NET;
+        Batch &B = e->batch[h];
+        // at least one counter, so the memset never sees a null buffer on a fresh engine;
+        // tail mode runs up to iters + 1 passes in chunks of kTailChunk
+        const uint32_t nc = std::max<uint32_t>(c.iters, 1) + (tail ? kTailChunk + 1 : 0);
+        DevBuf<uint32_t> *ctr[3] = {&B.iter_counts, c.cache.tab ? &B.iter_hits : nullptr,
+                                    tail ? &B.iter_more : nullptr};
+        for (DevBuf<uint32_t> *b : ctr) {   // (hits: the leaves served from the cache; more: capped tail passes)
+            if (!b) continue;
+            if (b->n < nc) SPAI_TRY(b->alloc(nc));
+            SPAI_HIP(hipMemsetAsync(b->p, 0, (size_t)nc * 4, st));
+        }
+    }
+    SPAI_HIP(hipMemcpyAsync(e->active.p, trees, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    SPAI_HIP(hipMemsetAsync(e->err.p, 0, 4, st));
+    SPAI_HIP(hipMemsetAsync(e->trees.evals.p, 0, ((size_t)e->trees.n_trees + 2) * 4, st));
+    // fork: the chains 1.. that have trees start after the setup on the engine stream
+    if (n > chains[0].cnt) SPAI_HIP(hipEventRecord(e->ev_fork, st));
+    for (int h = 1; h < nchain; ++h)
+        if (chains[h].cnt) SPAI_HIP(hipStreamWaitEvent(e->chain_stream[h], e->ev_fork, 0));
+    const TreeView tv = tree_view(e);
+    timed = timed && e->timer.enabled;
+    for (uint32_t it = 0; it < (tail ? 0u : iters); ++it) {
+        for (int h = 0; h < nchain; ++h) {
+            const Chain &c = chains[h];
+            if (!c.cnt || it >= c.iters) continue;
+            const hipStream_t sh = e->chain_stream[h];
+            const BatchView bv = batch_view(e, h, it, c.cache.tab);
+            const uint32_t nh = c.cnt, g8 = (nh + kTreesPerBlock - 1) / kTreesPerBlock;
+            const uint32_t *act = e->active.p + c.off;
+            const bool sample = timed && (it % e->timer.stride == 0);
+            if (it == 0) {
+                if (sample) SPAI_TRY(timer_record(e, 0, it, true, sh, h));
+                k_select<false><<<g8, kBlock, 0, sh>>>(tv, bv, c.cache, act, nh, e->cfg.c, e->err.p, 0u);
+                if (sample) SPAI_TRY(timer_record(e, 0, it, false, sh, h));
+            }
+            if (sample) SPAI_TRY(timer_record(e, 1, it, true, sh, h));
+            SPAI_TRY(evaluate(c, sh, bv, grid_cap, std::max(conc, 1)));
+            if (sample) SPAI_TRY(timer_record(e, 1, it, false, sh, h));
+            if (it + 1 < c.iters) {
+                const bool s2 = timed && ((it + 1) % e->timer.stride == 0);
+                if (s2) SPAI_TRY(timer_record(e, 0, it + 1, true, sh, h));
+                k_expand_select<false><<<g8, kBlock, 0, sh>>>(tv, bv, batch_view(e, h, it + 1, c.cache.tab), c.cache,
+                                                              act, nh, e->cfg.c, e->err.p, 0u);
+                if (s2) SPAI_TRY(timer_record(e, 0, it + 1, false, sh, h));
+            } else {
+                if (sample) SPAI_TRY(timer_record(e, 2, it, true, sh, h));
+                k_expand<<<g8, kBlock, 0, sh>>>(tv, bv, c.cache, nh, e->err.p);
+                if (sample) SPAI_TRY(timer_record(e, 2, it, false, sh, h));
+            }
+        }
+    }
+    SPAI_HIP(hipGetLastError());
+    for (int h = 1; h < nchain; ++h) {   // join
+        if (!chains[h].cnt) continue;
+        SPAI_HIP(hipEventRecord(e->ev_join[h], e->chain_stream[h]));
+        SPAI_HIP(hipStreamWaitEvent(st, e->ev_join[h], 0));
+    }
+    return SPAI_OK;
+}
 
 // Enqueue one search call over n >= 1 validated trees (mcts.rs:214-285 per tree),
 // up to the join of its chains on the engine stream.  Only tail mode waits (once
 // per chunk of passes, for its stop condition).
 int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, SearchRun &R) {
-    Trees &T = e->trees;
     const int kind = (int)e->cfg.eval;
     hipStream_t st = e->stream;
     // evaluation cache: allocated on first use; emptied here, between search calls
     // (no chain runs), once it is more than 3/4 full, so a long stream keeps hitting
     SPAI_TRY(cache_prepare(e, kind == SPAI_EVAL_NET));
-    if (e->cache.buckets && (uint64_t)e->cache.fill_seen * 4 > e->cache.entries() * 3) SPAI_TRY(cache_clear(e));
+    if (cache_nearly_full(e->cache)) SPAI_TRY(cache_clear(e));
     // tail mode (select_tree RUN_ON, one chain): late in a game, when in the previous
     // search call of these trees no tree evaluated SPAI_TAIL_TREE_EVALS leaves or
     // more (a pass per live leaf of the busiest tree: few passes), or the call
@@ -1040,46 +966,16 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
     const uint32_t tail_run =
         tr_env ? (uint32_t)std::max(1, std::atoi(tr_env)) : (solved ? std::max(num_searches, 1u) : kTailRun);
     const uint32_t tail_chunk = solved ? 1u : kTailChunk;
-    // chain h searches active[off[h] .. off[h] + cnt[h]) on chain_stream[h]
+    // chain h searches an even share of the trees, in order
     const ChainPolicy pol = tail ? ChainPolicy{1, 0u} : chains_for(n, e->last_evals_per_iter);
-    const int nchain = pol.chains;
-    uint32_t off[spai_engine::kChains] = {0, 0, 0, 0};
-    uint32_t *cnt = R.cnt;
-    R.nchain = nchain;
-    R.tail = tail;
-    for (int h = 0; h < nchain; ++h) {
-        off[h] = (uint32_t)((uint64_t)n * h / nchain);
-        cnt[h] = (uint32_t)((uint64_t)n * (h + 1) / nchain) - off[h];
-    }
-    for (int h = 0; h < nchain; ++h) {   // per-iteration leaf counters (also the batch slot counters)
-        Batch &B = e->batch[h];
-        // at least one counter even for num_searches == 0, so the memset never sees a
-        // null buffer on a fresh engine; tail mode runs up to num_searches + 1 passes
-        // in chunks of kTailChunk
-        const uint32_t nc = std::max<uint32_t>(num_searches, 1) + (tail ? kTailChunk + 1 : 0);
-        if (B.iter_counts.n < nc) SPAI_TRY(B.iter_counts.alloc(nc));
-        SPAI_HIP(hipMemsetAsync(B.iter_counts.p, 0, (size_t)nc * 4, st));
-        if (e->cache.buckets) {   // the per-iteration counters of the leaves served from the cache
-            if (B.iter_hits.n < nc) SPAI_TRY(B.iter_hits.alloc(nc));
-            SPAI_HIP(hipMemsetAsync(B.iter_hits.p, 0, (size_t)nc * 4, st));
-        }
-        if (tail) {
-            if (B.iter_more.n < nc) SPAI_TRY(B.iter_more.alloc(nc));
-            SPAI_HIP(hipMemsetAsync(B.iter_more.p, 0, (size_t)nc * 4, st));
-        }
-    }
-    SPAI_HIP(hipMemcpyAsync(e->active.p, tree_idx, n * 4, hipMemcpyHostToDevice, st));
-    SPAI_HIP(hipMemsetAsync(e->err.p, 0, 4, st));
-    SPAI_HIP(hipMemsetAsync(T.evals.p, 0, ((size_t)T.n_trees + 2) * 4, st));
-    if (nchain > 1) {   // fork: chains 1.. start after the setup on the engine stream
-        SPAI_HIP(hipEventRecord(e->ev_fork, st));
-        for (int h = 1; h < nchain; ++h) SPAI_HIP(hipStreamWaitEvent(e->chain_stream[h], e->ev_fork, 0));
-    }
-    const TreeView tv = tree_view(e);
+    const int nchain = R.nchain = pol.chains;
     const CacheView cv = cache_view(e);
-    const bool timed = e->timer.enabled && !tail;   // samples every chain's launches every stride-th iteration
-    uint32_t &n_counts = R.n_counts;   // leaf counters to read back per chain
-    n_counts = num_searches;
+    for (int h = 0; h < nchain; ++h) {
+        const uint32_t off = (uint32_t)((uint64_t)n * h / nchain);
+        R.chain[h] = Chain{off, (uint32_t)((uint64_t)n * (h + 1) / nchain) - off, num_searches, kind, e->net, cv};
+    }
+    SPAI_TRY(chains_launch(e, tree_idx, R.chain, nchain, pol.grid_cap, true, tail));
+    R.n_counts = num_searches;   // leaf counters to read back per chain
     if (tail) {
         // passes on the engine stream: select(0), then per pass p: evaluate(p),
         // expand(p) + select(p + 1), each select running its trees on through
@@ -1087,21 +983,18 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
         // no leaf and caps no tree leaves no tree with iterations to run (a tree
         // stops a launch only at a live leaf or the cap), so the host checks every
         // tail_chunk passes and stops there.
+        const TreeView tv = tree_view(e);
         const uint32_t g8 = (n + kTreesPerBlock - 1) / kTreesPerBlock;
         const uint32_t *act = e->active.p;
         k_set_left<<<(n + 255) / 256, 256, 0, st>>>(tv, act, n, num_searches);
-        k_select<true><<<g8, kBlock, 0, st>>>(tv, batch_view(e, 0, 0), cv, act, n, e->cfg.c, e->err.p, tail_run);
+        k_select<true><<<g8, kBlock, 0, st>>>(tv, batch_view(e, 0, 0, cv.tab), cv, act, n, e->cfg.c, e->err.p, tail_run);
         uint32_t p = 0, next = 1, more = 0, next_hits = 0;
         for (;;) {
             for (uint32_t q = 0; q < tail_chunk; ++q, ++p) {
-                const BatchView bv = batch_view(e, 0, p);
-                if (kind == SPAI_EVAL_NET) {
-                    SPAI_TRY(net_eval_batch(e->net, st, bv.count, n, bv.mine, bv.theirs, bv.priors, bv.value, 0));
-                } else {
-                    k_eval_stub<<<(n + kBlock - 1) / kBlock, kBlock, 0, st>>>(bv, n, kind);
-                }
-                k_expand_select<true><<<g8, kBlock, 0, st>>>(tv, bv, batch_view(e, 0, p + 1), cv, act, n, e->cfg.c,
-                                                             e->err.p, tail_run);
+                const BatchView bv = batch_view(e, 0, p, cv.tab);
+                SPAI_TRY(evaluate(R.chain[0], st, bv, 0u, 1));
+                k_expand_select<true><<<g8, kBlock, 0, st>>>(tv, bv, batch_view(e, 0, p + 1, cv.tab), cv, act, n,
+                                                             e->cfg.c, e->err.p, tail_run);
             }
             SPAI_HIP(hipGetLastError());
             SPAI_HIP(hipMemcpyAsync(&next, e->batch[0].iter_counts.p + p, 4, hipMemcpyDeviceToHost, st));
@@ -1114,51 +1007,24 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
             SPAI_CHECK(p <= num_searches + 1, SPAI_ERR_INVALID, "internal: tail passes exceed the iterations");
             // this chunk's counters are read back below; the next chunk's are fresh
         }
-        n_counts = p;
+        R.n_counts = p;
     }
-    e->last_tail_passes = tail ? n_counts : 0;
-    // per chain: select(0); then per iteration: evaluate(it), expand(it)+select(it+1)
-    // fused, and expand alone after the last evaluation.  Timer 0 samples the
-    // select-bearing launch (k_select / k_expand_select), 2 the last k_expand.
-    for (uint32_t it = 0; it < (tail ? 0u : num_searches); ++it) {
-        for (int h = 0; h < nchain; ++h) {
-            const hipStream_t sh = e->chain_stream[h];
-            const BatchView bv = batch_view(e, h, it);
-            const uint32_t nh = cnt[h], g8 = (nh + kTreesPerBlock - 1) / kTreesPerBlock;
-            const uint32_t *act = e->active.p + off[h];
-            const bool sample = timed && (it % e->timer.stride == 0);
-            if (it == 0) {
-                if (sample) SPAI_TRY(timer_record(e, 0, it, true, sh, h));
-                k_select<false><<<g8, kBlock, 0, sh>>>(tv, bv, cv, act, nh, e->cfg.c, e->err.p, 0u);
-                if (sample) SPAI_TRY(timer_record(e, 0, it, false, sh, h));
-            }
-            if (sample) SPAI_TRY(timer_record(e, 1, it, true, sh, h));
-            if (kind == SPAI_EVAL_NET) {
-                SPAI_TRY(net_eval_batch(e->net, sh, bv.count, nh, bv.mine, bv.theirs, bv.priors, bv.value,
-                                        pol.grid_cap, nchain));
-            } else {
-                k_eval_stub<<<(nh + kBlock - 1) / kBlock, kBlock, 0, sh>>>(bv, nh, kind);
-            }
-            if (sample) SPAI_TRY(timer_record(e, 1, it, false, sh, h));
-            if (it + 1 < num_searches) {
-                const bool s2 = timed && ((it + 1) % e->timer.stride == 0);
-                if (s2) SPAI_TRY(timer_record(e, 0, it + 1, true, sh, h));
-                k_expand_select<false><<<g8, kBlock, 0, sh>>>(tv, bv, batch_view(e, h, it + 1), cv, act, nh,
-                                                              e->cfg.c, e->err.p, 0u);
-                if (s2) SPAI_TRY(timer_record(e, 0, it + 1, false, sh, h));
-            } else {
-                if (sample) SPAI_TRY(timer_record(e, 2, it, true, sh, h));
-                k_expand<<<g8, kBlock, 0, sh>>>(tv, bv, cv, nh, e->err.p);
-                if (sample) SPAI_TRY(timer_record(e, 2, it, false, sh, h));
-            }
-        }
-    }
-    SPAI_HIP(hipGetLastError());
-    for (int h = 1; h < nchain; ++h) {   // join
-        SPAI_HIP(hipEventRecord(e->ev_join[h], e->chain_stream[h]));
-        SPAI_HIP(hipStreamWaitEvent(st, e->ev_join[h], 0));
-    }
+    e->last_tail_passes = tail ? R.n_counts : 0;
     return SPAI_OK;
+}
+
+int check_device_errors(spai_engine *e, uint32_t err) {
+    SPAI_CHECK(!(err & kErrCapacity), SPAI_ERR_CAPACITY, "node arena full (cap %u per tree)", e->trees.cap);
+    SPAI_CHECK(!(err & kErrDepth), SPAI_ERR_CAPACITY, "tree deeper than %d", kMaxDepth);
+    SPAI_CHECK(!(err & kErrNan), SPAI_ERR_NAN, "NaN UCB in select (reference: partial_cmp().unwrap() panics)");
+    return SPAI_OK;
+}
+
+void cache_account(spai_engine *e, double served, double forwarded, uint32_t fill) {
+    if (!e->cache.buckets) return;
+    e->cache.lookups += served;
+    e->cache.hits += served - forwarded;
+    e->cache.fill_seen = fill;
 }
 
 // The call's bookkeeping once its counters [chain][n_counts], error flags and
@@ -1170,43 +1036,18 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
 // policy goes by the served leaves: a tree's tail passes are its live leaves, whoever
 // answers them.
 int search_finish(spai_engine *e, const SearchRun &R, uint32_t num_searches, const uint32_t *ch_counts, uint32_t err,
-                  uint32_t max_tree_evals, double served, uint32_t cache_fill, double *evals_out) {
-    SPAI_TRY(timer_collect(e, ch_counts, R.n_counts, R.cnt));
+                  uint32_t max_tree_evals, double served, uint32_t cache_fill) {
+    SPAI_TRY(timer_collect(e, ch_counts, R.n_counts, R.chain));
     double s = 0;
     for (int h = 0; h < R.nchain; ++h)
         for (uint32_t i = 0; i < R.n_counts; ++i) s += ch_counts[(size_t)h * R.n_counts + i];
-    SPAI_CHECK(!(err & kErrCapacity), SPAI_ERR_CAPACITY, "node arena full (cap %u per tree)", e->trees.cap);
-    SPAI_CHECK(!(err & kErrDepth), SPAI_ERR_CAPACITY, "tree deeper than %d", kMaxDepth);
-    SPAI_CHECK(!(err & kErrNan), SPAI_ERR_NAN, "NaN UCB in select (reference: partial_cmp().unwrap() panics)");
-    if (evals_out) *evals_out = served;
-    if (e->cache.buckets) {
-        e->cache.lookups += served;
-        e->cache.hits += served - s;
-        e->cache.fill_seen = cache_fill;
-    }
+    SPAI_TRY(check_device_errors(e, err));
+    cache_account(e, served, s, cache_fill);
     e->last_evals_per_iter = num_searches ? s / num_searches : -1;
     e->last_served_per_iter = num_searches ? served / num_searches : -1;
     e->last_max_tree_evals = max_tree_evals;
     return SPAI_OK;
 }
-
-// the device buffer of a move step's records and its two pinned host copies (move
-// m's is read while m + 1 runs), at least n_words each
-int move_buffers(spai_engine *e, size_t n_words) {
-    if (e->h_move_n >= n_words) return SPAI_OK;
-    e->h_move_n = 0;
-    for (uint32_t *&h : e->h_move) {
-        if (h) (void)hipHostFree(h);
-        h = nullptr;
-        void *ph = nullptr;
-        SPAI_HIP(hipHostMalloc(&ph, n_words * 4, hipHostMallocDefault));
-        h = (uint32_t *)ph;
-    }
-    SPAI_TRY(e->move_out.alloc(n_words));
-    e->h_move_n = n_words;
-    return SPAI_OK;
-}
-}  // namespace
 
 int search(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, float *policy,
            uint32_t *child_ids, float *child_visits, uint32_t *n_children, double *evals_out) {
@@ -1236,8 +1077,8 @@ int search(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_se
                                     n_counts * 4, hipMemcpyDeviceToHost, st));
     SPAI_HIP(hipMemcpyAsync(&err, e->err.p, 4, hipMemcpyDeviceToHost, st));
     SPAI_HIP(hipStreamSynchronize(st));
-    SPAI_TRY(search_finish(e, R, num_searches, ch_counts.data(), err, tree_evals[0], (double)tree_evals[1], cache_fill,
-                           evals_out));
+    SPAI_TRY(search_finish(e, R, num_searches, ch_counts.data(), err, tree_evals[0], tree_evals[1], cache_fill));
+    if (evals_out) *evals_out = (double)tree_evals[1];
     // root visit policy (mcts.rs:310-331)
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t t = tree_idx[i];
@@ -1310,611 +1151,6 @@ int tree_size(spai_engine *e, uint32_t t, uint32_t *nodes) {
     return SPAI_OK;
 }
 
-// SelfPlayWorker::self_play (learner_concurrent.rs:169-242).  Per move: the search
-// call, then k_advance samples every game's move on the device and moves its
-// root, and one pinned copy brings back the records.  The next move's search is
-// launched as soon as the host knows which games go on; this move's bookkeeping
-// (policy targets, histories, finished games to the sink, in the reference's
-// order) runs on the host while it searches.
-// window < n_games (spai_selfplay_stream): the games run through `window` tree
-// slots; a slot whose game ended takes the next game before the next search call.
-// Each game's draws are keyed by its id and its own move number (per slot on the
-// device), so every game is the one spai_selfplay_run would play.
-int selfplay_run(spai_engine *e, uint32_t n_games, uint64_t gid_base, spai_sample_sink sink, void *user,
-                 spai_selfplay_stats *stats, uint32_t window) {
-    const auto t_start = std::chrono::steady_clock::now();
-    const uint32_t W = (window == 0 || window >= n_games) ? n_games : window;   // tree slots
-    SPAI_TRY(trees_create(e, W));
-    SPAI_CHECK(e->cfg.eval != SPAI_EVAL_NET || e->net, SPAI_ERR_INVALID,
-               "eval = NET but no net set (spai_engine_set_net)");
-    Trees &T = e->trees;
-    hipStream_t st = e->stream;
-    const uint32_t ns = e->cfg.num_searches;
-    // every game's history in flat per-game slabs of the longest game (42 plies):
-    // growing 3 x n_games vectors made every game reallocate at the same moves
-    constexpr size_t kPlies = c4::kCells;
-    // (visits as f32).powf(T) for every count a root child can reach (a search call
-    // adds at most ns visits to a root, a game has at most kPlies moves), by the
-    // host's powf (the f32::powf of the reference), once per temperature
-    const uint32_t pow_n = ns * (uint32_t)kPlies + 1;
-    const float temp = e->cfg.temperature;
-    if (e->pow_tab_t != temp || e->pow_tab.n < pow_n) {
-        std::vector<float> tab(pow_n);
-        for (uint32_t k = 0; k < pow_n; ++k) tab[k] = ::powf((float)k, temp);   // Rust f32::powf = libm powf
-        e->pow_tab_t = -1.0f;
-        SPAI_TRY(e->pow_tab.alloc(pow_n));
-        SPAI_HIP(hipMemcpy(e->pow_tab.p, tab.data(), pow_n * sizeof(float), hipMemcpyHostToDevice));
-        e->pow_tab_t = temp;
-    }
-    // records, then every chain's leaf counters (tail mode: up to ns + kTailChunk + 1)
-    SPAI_TRY(move_buffers(e, 2 + (size_t)W * kMoveRec +
-                                 (size_t)spai_engine::kChains * (std::max(ns, 1u) + kTailChunk + 1)));
-    std::vector<c4::State> h_states((size_t)W * kPlies);   // per tree slot
-    std::vector<float> h_pol((size_t)W * kPlies * 7);
-    std::vector<int32_t> h_moves((size_t)W * kPlies);
-    std::vector<uint32_t> h_len(W, 0);
-    std::vector<uint32_t> act[2];   // this move's trees and the next move's (the launch reads them)
-    act[0].resize(W);
-    for (uint32_t i = 0; i < W; ++i) act[0][i] = i;
-    std::vector<uint32_t> slot_game(W);   // the game (index < n_games) each slot plays
-    for (uint32_t i = 0; i < W; ++i) slot_game[i] = i;
-    uint32_t next_game = W;
-    std::vector<uint32_t> refill[2];   // per move parity: [slots..., games...] uploaded for k_slots_start
-    std::vector<float> enc, sv;
-    double sims = 0, evals = 0, games = 0, positions = 0, moves = 0;
-    // optional per-move trace (diagnostics): SPAI_TRACE_MOVES=<csv path>
-    FILE *trace = nullptr;
-    if (const char *tp = std::getenv("SPAI_TRACE_MOVES")) trace = std::fopen(tp, "a");
-    struct TraceClose {
-        FILE *f;
-        ~TraceClose() {
-            if (f) std::fclose(f);
-        }
-    } trace_close{trace};
-    const TreeView tv = tree_view(e);
-    const RootsOut ro{T.root.p, T.root_x.p, T.root_o.p, T.root_n.p, T.root_status.p};
-    SearchRun R;
-    // every slot starts its first game (id gid_base + slot) at move 0
-    k_slots_start<<<(W + 255) / 256, 256, 0, st>>>(tv, ro, T.slot_gid.p, T.slot_move.p, nullptr, W, gid_base);
-    SPAI_HIP(hipGetLastError());
-    // enqueue a move over the trees a: slots in rf start their new games, the search
-    // call, k_advance, the records' copy to dst
-    auto launch = [&](const std::vector<uint32_t> &a, const std::vector<uint32_t> &rf, uint32_t *dst) -> int {
-        const uint32_t na = (uint32_t)a.size();
-        if (!rf.empty()) {
-            const uint32_t nr = (uint32_t)(rf.size() / 2);
-            SPAI_HIP(hipMemcpyAsync(T.refill.p, rf.data(), rf.size() * 4, hipMemcpyHostToDevice, st));
-            k_slots_start<<<(nr + 255) / 256, 256, 0, st>>>(tv, ro, T.slot_gid.p, T.slot_move.p, T.refill.p, nr,
-                                                           gid_base);
-        }
-        SPAI_TRY(search_launch(e, na, a.data(), ns, R));
-        ChainCounts cc{};
-        for (int h = 0; h < R.nchain; ++h) cc.p[h] = e->batch[h].iter_counts.p;
-        k_advance<<<(na + 63) / 64, 64, 0, st>>>(tv, ro, e->active.p, na, e->pow_tab.p, (uint32_t)e->pow_tab.n,
-                                                 e->cfg.seed, T.slot_gid.p, T.slot_move.p, e->err.p,
-                                                 e->cache.buckets ? e->cache.ctr.p : nullptr, cc, R.nchain, R.n_counts,
-                                                 e->move_out.p);
-        SPAI_HIP(hipGetLastError());
-        const size_t words = 2 + (size_t)na * kMoveRec + (size_t)R.nchain * R.n_counts;
-        SPAI_HIP(hipMemcpyAsync(dst, e->move_out.p, words * 4, hipMemcpyDeviceToHost, st));
-        return SPAI_OK;
-    };
-    // every return below, errors included, leaves the engine quiescent: the next
-    // move's search, k_advance and the record copy may be in flight when a
-    // bookkeeping check fails (they write device roots and a pinned buffer)
-    struct Quiesce {
-        spai_engine *e;
-        ~Quiesce() {
-            (void)hipStreamSynchronize(e->stream);
-            for (hipStream_t cs : e->chain_stream)
-                if (cs) (void)hipStreamSynchronize(cs);
-        }
-    } quiesce{e};
-    uint64_t move_no = 0;
-    int cur = 0;
-    auto tm0 = std::chrono::steady_clock::now();
-    SPAI_TRY(launch(act[0], refill[0], e->h_move[0]));
-    while (!act[cur].empty()) {
-        const std::vector<uint32_t> &A = act[cur];
-        const uint32_t na = (uint32_t)A.size();
-        const uint32_t *mo = e->h_move[move_no & 1];
-        SPAI_HIP(hipStreamSynchronize(st));
-        const auto tm1 = std::chrono::steady_clock::now();
-        const uint32_t passes = e->last_tail_passes;
-        uint32_t max_ev = 0;
-        double served = 0;   // live leaves of the call over its trees (hits of the evaluation cache included)
-        bool stop = false;   // a game without a move: its error is raised in the bookkeeping below
-        for (uint32_t i = 0; i < na; ++i) {
-            const uint32_t *rec = mo + 2 + (size_t)i * kMoveRec;
-            max_ev = std::max(max_ev, rec[9]);
-            served += rec[9];
-            stop |= (rec[8] & kPickNone) != 0;
-        }
-        double ev = 0;
-        SPAI_TRY(search_finish(e, R, ns, mo + 2 + (size_t)na * kMoveRec, mo[0], max_ev, served, mo[1], &ev));
-        const double fwd_leaves = e->last_evals_per_iter * ns;
-        sims += (double)na * ns;
-        evals += ev;
-        moves += 1;
-        // the games that go on, in order (trees_vec.remove keeps it), and their next move;
-        // streaming: slots whose game ended take the next games (appended)
-        std::vector<uint32_t> &N = act[cur ^ 1];
-        std::vector<uint32_t> &RF = refill[(move_no + 1) & 1];
-        N.clear();
-        RF.clear();
-        auto tm2 = tm1;
-        if (!stop) {
-            for (uint32_t i = 0; i < na; ++i)
-                if (((mo[2 + (size_t)i * kMoveRec + 8] >> 16) & 0xFFu) == c4::kOngoing) N.push_back(A[i]);
-            for (uint32_t i = 0; i < na && next_game < n_games; ++i)
-                if (((mo[2 + (size_t)i * kMoveRec + 8] >> 16) & 0xFFu) != c4::kOngoing) {
-                    RF.push_back(A[i]);
-                    RF.push_back(next_game++);
-                }
-            const size_t nr = RF.size() / 2;
-            if (nr) {   // [slots..., games...]
-                std::vector<uint32_t> tmp(RF);
-                for (size_t j = 0; j < nr; ++j) {
-                    RF[j] = tmp[2 * j];
-                    RF[nr + j] = tmp[2 * j + 1];
-                    N.push_back(RF[j]);
-                }
-            }
-            tm2 = std::chrono::steady_clock::now();
-            if (!N.empty()) SPAI_TRY(launch(N, RF, e->h_move[(move_no + 1) & 1]));
-        }
-        const auto tm3 = std::chrono::steady_clock::now();
-        for (int k = (int)na - 1; k >= 0; --k) {   // for i in (0..trees_vec.len()).rev()
-            const uint32_t t = A[k];
-            const uint32_t *rec = mo + 2 + (size_t)k * kMoveRec;
-            const uint32_t w = rec[0], pick = rec[8];
-            if (pick & kPickNone) {
-                SPAI_CHECK((pick & 0xFFu) != kPickNoTable, SPAI_ERR_INVALID,
-                           "internal: game %u has a visit count beyond the visits^T table", t);
-                SPAI_CHECK(false, SPAI_ERR_NAN, "WeightedIndex over all-zero visit counts (game %u)", t);
-            }
-            const uint32_t nch = w == kNoChildren ? 0 : w >> 24, first = w & 0xFFFFFFu;
-            T.h_root_first[t] = first;
-            T.h_root_nch[t] = (uint8_t)nch;
-            const c4::State rs = T.h_root_state[t];
-            const uint32_t legal = c4::legal_mask(rs.x, rs.o, rs.status);
-            float pol[c4::kActions] = {0, 0, 0, 0, 0, 0, 0};   // root visit policy (mcts.rs:310-331)
-            for (uint32_t j = 0; j < nch; ++j) pol[c4::kth_bit(legal, (int)j)] = (float)rec[1 + j];
-            const int idx = (int)(pick & 0xFFu), a = (int)((pick >> 8) & 0xFFu);
-            c4::State cs;
-            SPAI_CHECK((uint32_t)idx < nch && a == c4::kth_bit(legal, idx) && c4::next_state(rs, a, cs) == 0 &&
-                           cs.status == ((pick >> 16) & 0xFFu),
-                       SPAI_ERR_INVALID, "internal: game %u's device move does not replay", t);
-            const size_t m = ++h_len[t];   // plies so far, this one included
-            SPAI_CHECK(m <= kPlies, SPAI_ERR_INVALID, "internal: game %u longer than %zu plies", t, kPlies);
-            c4::State *hs = h_states.data() + (size_t)t * kPlies;
-            float *hp = h_pol.data() + (size_t)t * kPlies * 7;
-            int32_t *hm = h_moves.data() + (size_t)t * kPlies;
-            hs[m - 1] = rs;
-            normalize_policy(pol, hp + (m - 1) * 7);
-            hm[m - 1] = a;
-            if (cs.status != c4::kOngoing) {                  // is_terminal: emit, trees_vec.remove(i)
-                const float v = c4::terminal_value(cs.status);
-                enc.assign(sink ? m * 126 : 0, 0.f);
-                sv.resize(m);
-                for (size_t j = 0; j < (sink ? m : 0); ++j) {
-                    const c4::State &s = hs[j];
-                    const bool xm = c4::x_to_move(s.n);
-                    const uint64_t mine = xm ? s.x : s.o, theirs = xm ? s.o : s.x;
-                    for (int r = 0; r < 6; ++r)
-                        for (int cc = 0; cc < 7; ++cc) {
-                            const int b = cc * 7 + r, cell = r * 7 + cc;
-                            if ((mine >> b) & 1) enc[j * 126 + cell] = 1.f;
-                            else if ((theirs >> b) & 1) enc[j * 126 + 42 + cell] = 1.f;
-                            else enc[j * 126 + 84 + cell] = 1.f;
-                        }
-                    // x.get_current_player() == state.get_current_player() ? value : -value
-                    sv[j] = ((s.n & 1) == (cs.n & 1)) ? v : -v;
-                }
-                if (sink) sink(user, (uint32_t)(gid_base + slot_game[t]), (uint32_t)m, enc.data(), hp, sv.data(), hm);
-                games += 1;
-                positions += (double)m;
-                h_len[t] = 0;
-            } else {                                          // use_subtree(selected_id), already on the device
-                T.h_root[t] = first + (uint32_t)idx;
-                T.h_root_state[t] = cs;
-                T.h_root_nch[t] = 0;
-            }
-        }
-        {   // streaming: the refilled slots' host mirrors start their new games (k_slots_start
-            // reset the device side ahead of the search call already in flight)
-            const std::vector<uint32_t> &RFc = refill[(move_no + 1) & 1];
-            const size_t nr = RFc.size() / 2;
-            for (size_t j = 0; j < nr; ++j) {
-                const uint32_t t = RFc[j];
-                slot_game[t] = RFc[nr + j];
-                T.h_root[t] = 0;
-                T.h_root_state[t] = c4::State{0, 0, 0, c4::kOngoing};
-                T.h_root_first[t] = 0;
-                T.h_root_nch[t] = 0;
-            }
-        }
-        if (trace)   // move, active trees, leaves evaluated, search seconds (launch to records), host seconds
-                     // between the records and the next launch, search passes (tail mode; 0: one launch pair
-                     // per iteration), bookkeeping seconds (overlapping the next search), leaves the forward
-                     // ran (the rest of the evaluated ones came from the evaluation cache)
-            std::fprintf(trace, "%llu,%u,%.0f,%.6f,%.6f,%u,%.6f,%.0f\n", (unsigned long long)move_no, na, ev,
-                         std::chrono::duration<double>(tm1 - tm0).count(),
-                         std::chrono::duration<double>(tm2 - tm1).count(), passes,
-                         std::chrono::duration<double>(std::chrono::steady_clock::now() - tm3).count(), fwd_leaves);
-        tm0 = tm2;
-        cur ^= 1;
-        ++move_no;
-    }
-    if (stats) {
-        stats->sims = sims;
-        stats->evals = evals;
-        stats->games = games;
-        stats->positions = positions;
-        stats->moves = moves;
-        stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-    }
-    return SPAI_OK;
-}
-
-// ---------------------------------------------------------------- match
-// play() (main.rs:54-135) between two evaluators over many games (spai.h "match").
-// Game g of the call owns trees 2g (player A's) and 2g + 1 (B's).  The games run in
-// lockstep, so at every ply the games with A to move and those with B to move are
-// two disjoint tree lists: chain 0 searches A's with A's evaluator, chain 1 B's
-// with B's, side by side like the two halves of a self-play call.  Tail mode (a
-// one-chain schedule) stays off.
-namespace {
-// the opening of pair `pair`: ply k plays the idx-th legal column, idx from one f32 multiply
-__host__ __device__ inline c4::State opening_state(uint64_t seed, uint64_t pair, uint32_t plies, uint8_t *moves) {
-    c4::State s{0, 0, 0, c4::kOngoing};
-    for (uint32_t k = 0; k < plies; ++k) {
-        const uint32_t legal = c4::legal_mask(s.x, s.o, s.status);
-        const int n_legal = (int)c4::popc32(legal);
-        int idx = (int)(sample_u01_f32(seed, pair, k) * (float)n_legal);
-        idx = idx < n_legal - 1 ? idx : n_legal - 1;
-        const int a = c4::kth_bit(legal, idx);
-        c4::State ns = s;
-        (void)c4::next_state(s, a, ns);
-        s = ns;
-        if (moves) moves[k] = (uint8_t)a;
-    }
-    return s;
-}
-
-// both trees of every game: an empty arena whose root is the position after the opening
-__global__ void k_match_start(TreeView T, RootsOut R, uint32_t n_games, uint64_t gid_base, uint64_t seed,
-                              uint32_t plies) {
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_games) return;
-    const c4::State s = opening_state(seed, (gid_base + g) / 2, plies, nullptr);
-    for (uint32_t t = 2 * g; t < 2 * g + 2; ++t) {
-        T.nodes[(size_t)t * T.cap] = make_uint4(0u, 0u, 0u, kNoChildren);
-        T.next_free[t] = 1;
-        R.root[t] = 0;
-        R.x[t] = s.x;
-        R.o[t] = s.o;
-        R.n[t] = s.n;
-        R.status[t] = s.status;
-    }
-}
-
-// The move after a ply's search call, per searched tree t (the mover's; t ^ 1 is the
-// opponent's tree of the same game, at the same position): the most-visited root
-// child, ties to the last; for a game that goes on, the mover's tree re-rooted at it
-// (use_subtree) and the opponent's at the same action's child -- the same index, its
-// root being the same position -- or, while that root has no children (before the
-// second player's first search), started anew at the new position.  The record per
-// tree and the words around the records are k_advance's; rec[8] without a visited
-// child is kPickNone | 2 (the all-zero code of weighted_index_f32).  Chain h's
-// per-iteration leaf counts follow the records at counts[h * stride ..].
-struct MatchCounts {
-    const uint32_t *p[2];
-    uint32_t n[2];
-};
-__global__ void k_match_advance(TreeView T, RootsOut R, const uint32_t *__restrict__ active, uint32_t n_active,
-                                const uint32_t *err, const uint32_t *cache_fill, MatchCounts cc, uint32_t stride,
-                                uint32_t *out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (blockIdx.x == 0) {
-        if (threadIdx.x == 0) {
-            out[0] = *err;
-            out[1] = cache_fill ? *cache_fill : 0u;
-        }
-        uint32_t *counts = out + 2 + (size_t)n_active * kMoveRec;
-        for (int h = 0; h < 2; ++h)
-            for (uint32_t j = threadIdx.x; j < cc.n[h]; j += blockDim.x) counts[(size_t)h * stride + j] = cc.p[h][j];
-    }
-    if (i >= n_active) return;
-    const uint32_t t = active[i], opp = t ^ 1u;
-    uint4 *nodes = T.nodes + (size_t)t * T.cap;
-    const uint4 r = nodes[T.root[t]];
-    const uint32_t nch = r.w == kNoChildren ? 0 : r.w >> 24, first = r.w & 0xFFFFFFu;
-    uint32_t *rec = out + 2 + (size_t)i * kMoveRec;
-    rec[0] = r.w;
-    uint32_t best = 0;
-    int idx = -1;
-    for (uint32_t k = 0; k < (uint32_t)c4::kActions; ++k) {
-        const uint32_t v = k < nch ? nodes[first + k].x : 0u;
-        rec[1 + k] = v;
-        if (k < nch && v >= best) {
-            best = v;
-            idx = (int)k;
-        }
-    }
-    rec[9] = T.evals[t];
-    if (best == 0) {
-        rec[8] = kPickNone | 2u;
-        return;
-    }
-    const c4::State rs{T.root_x[t], T.root_o[t], T.root_n[t], T.root_status[t]};
-    const int a = c4::kth_bit(c4::legal_mask(rs.x, rs.o, rs.status), idx);
-    c4::State cs = rs;
-    (void)c4::next_state(rs, a, cs);
-    rec[8] = (uint32_t)idx | (uint32_t)a << 8 | (uint32_t)cs.status << 16;
-    if (cs.status != c4::kOngoing) return;
-    R.root[t] = first + (uint32_t)idx;
-    uint4 *onodes = T.nodes + (size_t)opp * T.cap;
-    const uint32_t ow = onodes[T.root[opp]].w;
-    if (ow != kNoChildren) {
-        R.root[opp] = (ow & 0xFFFFFFu) + (uint32_t)idx;
-    } else {
-        onodes[0] = make_uint4(0u, 0u, 0u, kNoChildren);
-        T.next_free[opp] = 1;
-        R.root[opp] = 0;
-    }
-    for (uint32_t u = t & ~1u; u < (t & ~1u) + 2; ++u) {
-        R.x[u] = cs.x;
-        R.o[u] = cs.o;
-        R.n[u] = cs.n;
-        R.status[u] = cs.status;
-    }
-}
-
-struct MatchSide {
-    int kind;
-    spai_net *net;
-    uint32_t iters;
-    uint32_t gen;   // its generation in the evaluation cache
-};
-
-// One ply's search call: chain h runs trees[off h .. off h + cnt[h]) (player h's) for
-// side[h].iters iterations with side[h]'s evaluator, up to the join on the engine
-// stream.  A chain without trees launches nothing.  The launches per chain are
-// search_launch's (select; evaluate, expand + select ...; evaluate, expand).
-int match_search_launch(spai_engine *e, const uint32_t *trees, const uint32_t (&cnt)[2], const MatchSide (&side)[2]) {
-    Trees &T = e->trees;
-    hipStream_t st = e->stream;
-    const uint32_t n = cnt[0] + cnt[1];
-    const uint32_t off[2] = {0, cnt[0]};
-    bool cached[2];
-    int nets = 0;   // chains whose forwards share the CUs
-    for (int h = 0; h < 2; ++h) {
-        cached[h] = e->cache.buckets && side[h].kind == SPAI_EVAL_NET;
-        if (!cnt[h]) continue;
-        nets += side[h].kind == SPAI_EVAL_NET;
-        Batch &B = e->batch[h];
-        const uint32_t nc = side[h].iters;
-        if (B.iter_counts.n < nc) SPAI_TRY(B.iter_counts.alloc(nc));
-        SPAI_HIP(hipMemsetAsync(B.iter_counts.p, 0, (size_t)nc * 4, st));
-        if (cached[h]) {
-            if (B.iter_hits.n < nc) SPAI_TRY(B.iter_hits.alloc(nc));
-            SPAI_HIP(hipMemsetAsync(B.iter_hits.p, 0, (size_t)nc * 4, st));
-        }
-    }
-    SPAI_HIP(hipMemcpyAsync(e->active.p, trees, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    SPAI_HIP(hipMemsetAsync(e->err.p, 0, 4, st));
-    SPAI_HIP(hipMemsetAsync(T.evals.p, 0, ((size_t)T.n_trees + 2) * 4, st));
-    if (cnt[1]) {
-        SPAI_HIP(hipEventRecord(e->ev_fork, st));
-        SPAI_HIP(hipStreamWaitEvent(e->chain_stream[1], e->ev_fork, 0));
-    }
-    const TreeView tv = tree_view(e);
-    auto bview = [&](int h, uint32_t it) {
-        BatchView b = batch_view(e, h, it);
-        if (!cached[h]) b.hits = nullptr;
-        return b;
-    };
-    const uint32_t iters = std::max(side[0].iters, side[1].iters);
-    for (uint32_t it = 0; it < iters; ++it) {
-        for (int h = 0; h < 2; ++h) {
-            if (!cnt[h] || it >= side[h].iters) continue;
-            const hipStream_t sh = e->chain_stream[h];
-            const CacheView cv = cached[h] ? CacheView{e->cache.table.p, e->cache.buckets - 1u, side[h].gen, e->cache.ctr.p}
-                                           : CacheView{nullptr, 0u, 0u, nullptr};
-            const BatchView bv = bview(h, it);
-            const uint32_t nh = cnt[h], g8 = (nh + kTreesPerBlock - 1) / kTreesPerBlock;
-            const uint32_t *act = e->active.p + off[h];
-            if (it == 0) k_select<false><<<g8, kBlock, 0, sh>>>(tv, bv, cv, act, nh, e->cfg.c, e->err.p, 0u);
-            if (side[h].kind == SPAI_EVAL_NET) {
-                SPAI_TRY(net_eval_batch(side[h].net, sh, bv.count, nh, bv.mine, bv.theirs, bv.priors, bv.value, 0u,
-                                        std::max(nets, 1)));
-            } else {
-                k_eval_stub<<<(nh + kBlock - 1) / kBlock, kBlock, 0, sh>>>(bv, nh, side[h].kind);
-            }
-            if (it + 1 < side[h].iters)
-                k_expand_select<false><<<g8, kBlock, 0, sh>>>(tv, bv, bview(h, it + 1), cv, act, nh, e->cfg.c,
-                                                              e->err.p, 0u);
-            else
-                k_expand<<<g8, kBlock, 0, sh>>>(tv, bv, cv, nh, e->err.p);
-        }
-    }
-    SPAI_HIP(hipGetLastError());
-    if (cnt[1]) {
-        SPAI_HIP(hipEventRecord(e->ev_join[1], e->chain_stream[1]));
-        SPAI_HIP(hipStreamWaitEvent(st, e->ev_join[1], 0));
-    }
-    return SPAI_OK;
-}
-}  // namespace
-
-int match_run(spai_engine *e, const spai_match_player *a, const spai_match_player *b, uint32_t n_games,
-              uint64_t gid_base, const spai_match_config *cfg, spai_match_game *games, spai_match_stats *stats) {
-    const auto t_start = std::chrono::steady_clock::now();
-    const uint32_t W = 2 * n_games;
-    SPAI_TRY(trees_create(e, W));
-    Trees &T = e->trees;
-    EvalCache &C = e->cache;
-    hipStream_t st = e->stream;
-    MatchSide side[2] = {{a->eval, a->net, a->num_searches, 0u}, {b->eval, b->net, b->num_searches, 0u}};
-    const uint32_t stride = std::max(side[0].iters, side[1].iters);
-    SPAI_TRY(move_buffers(e, 2 + (size_t)W * kMoveRec + 2 * (size_t)stride));
-    // Every return, errors included, leaves the streams idle (the next ply may be in
-    // flight when a check fails), the cache without the match's entries and the trees
-    // as trees_create leaves them (the host mirrors of the roots are not kept in a match).
-    struct Finish {
-        spai_engine *e;
-        uint32_t w;
-        ~Finish() {
-            (void)hipStreamSynchronize(e->stream);
-            for (hipStream_t cs : e->chain_stream)
-                if (cs) (void)hipStreamSynchronize(cs);
-            (void)cache_clear(e);
-            (void)trees_create(e, w);
-        }
-    } finish{e, W};
-    // The evaluation cache, on when a net plays: each player's entries carry a
-    // generation of their own, so neither is ever served the other's evaluations
-    // (one generation when both play the same net).  The table is emptied before the
-    // generations are drawn, so no older entry can carry either.
-    SPAI_TRY(cache_prepare(e, side[0].kind == SPAI_EVAL_NET || side[1].kind == SPAI_EVAL_NET));
-    const bool same_net = side[0].kind == SPAI_EVAL_NET && side[1].kind == SPAI_EVAL_NET && side[0].net == side[1].net;
-    auto new_gens = [&]() -> int {
-        SPAI_TRY(cache_clear(e));
-        side[0].gen = C.gen;
-        if (!same_net) C.gen = C.gen % 32767u + 1u;
-        side[1].gen = C.gen;
-        return SPAI_OK;
-    };
-    if (C.buckets) SPAI_TRY(new_gens());
-    const TreeView tv = tree_view(e);
-    const RootsOut ro{T.root.p, T.root_x.p, T.root_o.p, T.root_n.p, T.root_status.p};
-    k_match_start<<<(n_games + 255) / 256, 256, 0, st>>>(tv, ro, n_games, gid_base, cfg->seed, cfg->opening_plies);
-    SPAI_HIP(hipGetLastError());
-    // the host's record of every game: position, moves, outcome
-    std::vector<c4::State> pos(n_games);
-    std::vector<spai_match_game> rec_games(n_games);
-    for (uint32_t g = 0; g < n_games; ++g) {
-        spai_match_game &G = rec_games[g];
-        G = spai_match_game{};
-        G.game_id = gid_base + g;
-        G.a_moves_first = (int8_t)(((gid_base + g) & 1ull) == 0);
-        G.n_moves = (uint8_t)cfg->opening_plies;
-        pos[g] = opening_state(cfg->seed, (gid_base + g) / 2, cfg->opening_plies, G.moves);
-    }
-    // a ply's trees: player A's of the live games where A is to move, then B's of the others
-    struct Ply {
-        std::vector<uint32_t> trees;
-        uint32_t cnt[2] = {0, 0};
-    } ply[2];
-    auto build = [&](const std::vector<uint32_t> &live_games, uint32_t ply_no, Ply &P) {
-        P.trees.clear();
-        for (uint32_t p = 0; p < 2; ++p) {
-            for (uint32_t g : live_games)
-                if ((((gid_base + g) ^ ply_no) & 1ull) == p) P.trees.push_back(2 * g + p);
-            P.cnt[p] = (uint32_t)P.trees.size() - (p ? P.cnt[0] : 0u);
-        }
-    };
-    auto launch = [&](const Ply &P, uint32_t *dst) -> int {
-        if (C.buckets && (uint64_t)C.fill_seen * 4 > C.entries() * 3) SPAI_TRY(new_gens());
-        SPAI_TRY(match_search_launch(e, P.trees.data(), P.cnt, side));
-        const uint32_t na = (uint32_t)P.trees.size();
-        MatchCounts cc{};
-        for (int h = 0; h < 2; ++h) {
-            cc.p[h] = e->batch[h].iter_counts.p;
-            cc.n[h] = P.cnt[h] ? side[h].iters : 0u;
-        }
-        k_match_advance<<<(na + 63) / 64, 64, 0, st>>>(tv, ro, e->active.p, na, e->err.p,
-                                                       C.buckets ? C.ctr.p : nullptr, cc, stride, e->move_out.p);
-        SPAI_HIP(hipGetLastError());
-        const size_t words = 2 + (size_t)na * kMoveRec + 2 * (size_t)stride;
-        SPAI_HIP(hipMemcpyAsync(dst, e->move_out.p, words * 4, hipMemcpyDeviceToHost, st));
-        return SPAI_OK;
-    };
-    std::vector<uint32_t> live_games(n_games), next_games;
-    for (uint32_t g = 0; g < n_games; ++g) live_games[g] = g;
-    std::vector<uint8_t> ended(n_games, 0);
-    double sims[2] = {0, 0}, evals[2] = {0, 0};
-    uint32_t ply_no = cfg->opening_plies;
-    int cur = 0;
-    build(live_games, ply_no, ply[0]);
-    SPAI_TRY(launch(ply[0], e->h_move[0]));
-    while (!live_games.empty()) {
-        const Ply &P = ply[cur];
-        const uint32_t na = (uint32_t)P.trees.size();
-        const uint32_t *mo = e->h_move[cur];
-        SPAI_HIP(hipStreamSynchronize(st));
-        const uint32_t err = mo[0];
-        SPAI_CHECK(!(err & kErrCapacity), SPAI_ERR_CAPACITY, "node arena full (cap %u per tree)", T.cap);
-        SPAI_CHECK(!(err & kErrDepth), SPAI_ERR_CAPACITY, "tree deeper than %d", kMaxDepth);
-        SPAI_CHECK(!(err & kErrNan), SPAI_ERR_NAN, "NaN UCB in select (reference: partial_cmp().unwrap() panics)");
-        const uint32_t *counts = mo + 2 + (size_t)na * kMoveRec;
-        bool stop = false;
-        for (uint32_t p = 0, i = 0; p < 2; ++p) {
-            if (!P.cnt[p]) continue;
-            double served = 0, fwd = 0;
-            for (uint32_t k = 0; k < P.cnt[p]; ++k, ++i) {
-                const uint32_t *rec = mo + 2 + (size_t)i * kMoveRec;
-                served += rec[9];
-                stop |= (rec[8] & kPickNone) != 0;
-                ended[P.trees[i] / 2] = ((rec[8] >> 16) & 0xFFu) != c4::kOngoing;
-            }
-            for (uint32_t j = 0; j < side[p].iters; ++j) fwd += counts[(size_t)p * stride + j];
-            sims[p] += (double)P.cnt[p] * side[p].iters;
-            evals[p] += served;
-            if (C.buckets && side[p].kind == SPAI_EVAL_NET) {
-                C.lookups += served;
-                C.hits += served - fwd;
-            }
-        }
-        if (C.buckets) C.fill_seen = mo[1];
-        SPAI_CHECK(!stop, SPAI_ERR_NAN, "no visited root child to play (num_searches = 1 visits none)");
-        // the games that go on, in order, search their next ply while the host records this one
-        next_games.clear();
-        for (uint32_t g : live_games)
-            if (!ended[g]) next_games.push_back(g);
-        if (!next_games.empty()) {
-            build(next_games, ply_no + 1, ply[cur ^ 1]);
-            SPAI_TRY(launch(ply[cur ^ 1], e->h_move[cur ^ 1]));
-        }
-        for (uint32_t i = 0; i < na; ++i) {
-            const uint32_t t = P.trees[i], g = t / 2, p = t & 1u;
-            const uint32_t *rec = mo + 2 + (size_t)i * kMoveRec;
-            const uint32_t w = rec[0], pick = rec[8];
-            const uint32_t nch = w == kNoChildren ? 0 : w >> 24;
-            const c4::State rs = pos[g];
-            const uint32_t legal = c4::legal_mask(rs.x, rs.o, rs.status);
-            const int idx = (int)(pick & 0xFFu), mv = (int)((pick >> 8) & 0xFFu);
-            c4::State cs;
-            SPAI_CHECK((uint32_t)idx < nch && nch == c4::popc32(legal) && mv == c4::kth_bit(legal, idx) &&
-                           c4::next_state(rs, mv, cs) == 0 && cs.status == ((pick >> 16) & 0xFFu),
-                       SPAI_ERR_INVALID, "internal: game %u's device move does not replay", g);
-            spai_match_game &G = rec_games[g];
-            SPAI_CHECK(G.n_moves < c4::kCells, SPAI_ERR_INVALID, "internal: game %u longer than 42 plies", g);
-            G.moves[G.n_moves++] = (uint8_t)mv;
-            pos[g] = cs;
-            if (cs.status == c4::kWon) G.result_a = p == 0 ? 1 : -1;
-        }
-        live_games.swap(next_games);
-        cur ^= 1;
-        ++ply_no;
-    }
-    if (games)
-        for (uint32_t g = 0; g < n_games; ++g) games[g] = rec_games[g];
-    if (stats) {
-        *stats = spai_match_stats{};
-        for (const spai_match_game &G : rec_games) {
-            const int f = G.a_moves_first ? 0 : 1;
-            (G.result_a > 0 ? stats->a_wins : G.result_a < 0 ? stats->b_wins : stats->draws)[f] += 1;
-        }
-        for (int p = 0; p < 2; ++p) {
-            stats->sims[p] = sims[p];
-            stats->evals[p] = evals[p];
-        }
-        stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-    }
-    return SPAI_OK;
-}
 
 int eval_cache_set_capacity(spai_engine *e, uint64_t entries) {
     e->cache.user_set = true;

@@ -85,7 +85,7 @@ struct Trees {
     DevBuf<uint32_t> left;          // [n_trees] search iterations left (tail run-on mode, search.hip)
     DevBuf<uint32_t> evals;         // [n_trees] live leaves of the current search call (tail-mode policy)
     DevBuf<uint64_t> slot_gid;      // [n_trees] self-play: the game id a tree slot plays (its sampling stream)
-    DevBuf<uint32_t> slot_move;     // [n_trees] self-play: that game's move number (k_advance advances it)
+    DevBuf<uint32_t> slot_move;     // [n_trees] self-play: that game's move number (selfplay.hip k_advance advances it)
     DevBuf<uint32_t> refill;        // [2 n_trees] self-play streaming: slots taking a new game, and the games
     // host mirrors of the root bookkeeping
     std::vector<uint32_t> h_root;
@@ -243,7 +243,7 @@ struct spai_engine {
     spai::DevBuf<uint32_t> active;   // active tree list
     spai::DevBuf<uint32_t> err;      // device error flags
     spai::DevBuf<uint32_t> stats;    // root stats [n][8]
-    // self-play's move step on the device (search.hip k_advance): visits^T for every
+    // self-play's move step on the device (selfplay.hip k_advance; a match's: match.hip): visits^T for every
     // visit count a game can reach (the host's std::pow), and the per-move records,
     // read back into one of two pinned buffers (move m's is read while m + 1 runs)
     spai::DevBuf<float> pow_tab;       // (visit count as f32).powf(T), host glibc powf
@@ -325,7 +325,7 @@ int replay_size(spai_replay *r, uint32_t *n);
 void choose_multiple(uint32_t n, uint32_t k, uint64_t seed, uint64_t stream, std::vector<uint32_t> &out);
 int pipeline_run(const spai_pipeline_config *cfg, const float *init_params, size_t n_params, spai_pipeline_stats *st);
 
-// search.hip
+// search.hip (what it shares with selfplay.hip and match.hip alone: search_internal.h)
 int trees_create(spai_engine *e, uint32_t n);
 int tree_reset(spai_engine *e, uint32_t t, const spai_c4_state *root);
 int search(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, float *policy,
@@ -333,13 +333,15 @@ int search(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_se
 int tree_use_subtree(spai_engine *e, uint32_t t, uint32_t child);
 int tree_node(spai_engine *e, uint32_t t, uint32_t node, spai_c4_state *st, uint32_t *visits, float *w);
 int tree_size(spai_engine *e, uint32_t t, uint32_t *nodes);
+// selfplay.hip
 int selfplay_run(spai_engine *e, uint32_t n_games, uint64_t gid_base, spai_sample_sink sink, void *user,
                  spai_selfplay_stats *stats, uint32_t window = 0);
-// evaluation cache: capacity in entries (0: off), takes effect at the next search call;
+// search.hip, evaluation cache: capacity in entries (0: off), takes effect at the next search call;
 // clear it (weights changed: always with a new generation); counters
 int eval_cache_set_capacity(spai_engine *e, uint64_t entries);
 int eval_cache_clear(spai_engine *e);
 int eval_cache_stats(spai_engine *e, spai_eval_cache_stats *out);
+// match.hip
 int match_run(spai_engine *e, const spai_match_player *a, const spai_match_player *b, uint32_t n_games,
               uint64_t gid_base, const spai_match_config *cfg, spai_match_game *games, spai_match_stats *stats);
 

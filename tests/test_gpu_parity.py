@@ -407,7 +407,7 @@ def test_self_play_hash_matches_oracle(spai, oracle):
 
 @pytest.mark.parametrize("temperature", [0.7, 3.0])
 def test_self_play_device_sampling_matches_oracle(spai, oracle, temperature):
-    """the move step on the device (search.hip k_advance: Philox uniform,
+    """the move step on the device (selfplay.hip k_advance: Philox uniform,
     WeightedIndex over the std::pow table of visits^T, the new root written in
     place): at temperatures other than the default, and for a second run on the
     same engine (the table reused) at another game-id base, the sample stream is
@@ -453,7 +453,7 @@ def test_self_play_stream_temperature_matches_oracle(spai, oracle, temperature, 
     e.close()
 
 
-kTailChunk = 4   # search.hip: passes per host check
+kTailChunk = 4   # search_internal.h: passes per host check
 
 
 @pytest.mark.parametrize("tail_leaves,tail_tree,tail_run", [("8", "0", "64"), ("64", "0", "1000"), ("0", "1000", "64"),

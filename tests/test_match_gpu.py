@@ -69,6 +69,40 @@ def test_stub_players_bit_exact(spai, oracle, ref, stub_engine, n, plies, sa, sb
     assert sum(len(g["moves"]) for g in dev[0]) >= 7 * n
 
 
+def _selfplay_stub(e, n):
+    games, stats = e.self_play(n)
+    return ([(g["game"], g["moves"].tolist(), g["policy"].tobytes(), g["value"].tobytes()) for g in games],
+            stats["sims"], stats["evals"])
+
+
+def test_match_neither_samples_nor_disturbs_the_timers(spai, oracle, ref):
+    """self-play's search calls and a match's share one launcher; only the former sample
+    the engine's timers.  HASH against UNIFORM, 5 games, simulations (8, 24), 1 opening ply."""
+    a, b = (spai.EVAL_HASH, None, 8), (spai.EVAL_UNIFORM, None, 24)
+    engines = [spai.Engine(num_searches=24, max_trees=144, eval_kind=spai.EVAL_HASH) for _ in range(2)]
+    for e in engines:
+        e.set_timing(True, stride=1)
+    e, fresh = engines
+    before = {k: v["launches"] for k, v in e.timing().items()}
+    _same(e.match(a, b, 5, opening_plies=1, seed=11), ref.play_match(a, b, 5, 1, seed=11))
+    assert {k: v["launches"] for k, v in e.timing().items()} == before
+    after = _selfplay_stub(e, 5)
+    assert e.timing()["evaluate"]["launches"] > 0
+    assert after == _selfplay_stub(fresh, 5)
+    for e in engines:
+        e.close()
+
+
+def test_unequal_and_empty_chains(spai, oracle, ref, stub_engine):
+    """one game, simulations (24, 8), no opening: every ply has one chain without trees and
+    the other alternates between 24 and 8 iterations; then 72 games at (8, 24), both chains
+    full, on the same engine"""
+    h, u = spai.EVAL_HASH, spai.EVAL_UNIFORM
+    for n, sa, sb in ((1, 24, 8), (72, 8, 24)):
+        _same(stub_engine.match((h, None, sa), (u, None, sb), n, opening_plies=0, seed=11),
+              ref.play_match((h, None, sa), (u, None, sb), n, 0, seed=11))
+
+
 @pytest.mark.parametrize("n", [1, 5])
 def test_one_simulation_is_err_nan_on_both_sides(spai, oracle, ref, stub_engine, n):
     """simulations (1, 1): the only simulation expands the root and visits no child, so
