@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define SPAI_VERSION_MAJOR 0
-#define SPAI_VERSION_MINOR 2
+#define SPAI_VERSION_MINOR 3
 
 typedef enum spai_error {
     SPAI_OK = 0,
@@ -629,6 +629,39 @@ int spai_chess_selfplay_stream(spai_chess *e, uint32_t n_games, uint32_t window,
  * ms[0] select + leaf rules, ms[1] net forward, ms[2] expand + backup */
 int spai_chess_set_timing(spai_chess *e, int enabled);
 int spai_chess_timing(spai_chess *e, double *avg_ms, double *launches, double *items);
+
+/* weight refresh of a self-play net in place (the BN fold + fragment pack of
+ * spai_chess_net_create into the same allocations, stream-ordered behind any
+ * search still reading the old weights): forward afterwards is bit-identical to
+ * a net freshly created from the same parameters */
+int spai_chess_net_set_params(spai_chess_net *net, const float *params, size_t n_params);
+
+/* Device train step of the chess net (model/chess.rs:48-70 under
+ * model/mod.rs:128-141) in exact fp32 (f32 MFMA), on the engine's device and
+ * stream: train-mode forward (BatchNorm batch statistics in the trunk),
+ * loss = -(log_softmax(p) . pi).sum() / B + mean((v - z)^2), backward, one Adam
+ * step.  Parameters are the flat vector of spai_chess_net_num_params /
+ * spai_chess_net_init_params (BN running statistics included).  Deterministic:
+ * the same parameters and batches give bit-identical losses, gradients and
+ * parameters.  A non-finite loss returns SPAI_ERR_NAN. */
+typedef struct spai_chess_learner spai_chess_learner;
+int spai_chess_learner_create(spai_chess *e, int blocks, const float *params, size_t n_params,
+                              const spai_adam_config *cfg /* NULL = defaults */, spai_chess_learner **out);
+int spai_chess_learner_destroy(spai_chess_learner *l);
+/* states [n][19*64] (spai_chess_encode layout), policies [n][4672], values [n]; loss[3] = total, policy, value (may be NULL) */
+int spai_chess_learner_train_batch(spai_chess_learner *l, uint32_t n, const float *states, const float *policies,
+                                   const float *values, float *loss);
+/* Model::train: fresh Adam, one permutation (choose_multiple(n, n, seed, 0x7EA1B), as spai_learner_train),
+ * epochs x ceil(n/batch) steps, short last batch */
+int spai_chess_learner_train(spai_chess_learner *l, uint32_t n, const float *states, const float *policies,
+                             const float *values, uint32_t epochs, uint32_t batch, uint64_t seed, float *loss);
+int spai_chess_learner_params(spai_chess_learner *l, float *params, size_t n_params);
+int spai_chess_learner_grads(spai_chess_learner *l, float *grads, size_t n_params);
+/* the last train step's post-ReLU activations: layers 0 .. 2*blocks the trunk convs
+ * [B][256][64], 2*blocks+1 the first policy conv [B][256][64], 2*blocks+2 the value conv
+ * [B][64], 2*blocks+3 the first value linear [B][256] */
+int spai_chess_learner_activation(spai_chess_learner *l, int layer, float *out, size_t n);
+int spai_chess_learner_last_batch(spai_chess_learner *l, uint32_t *n);
 
 
 /* ---------------------------------------------------------------- tictactoe

@@ -1,0 +1,160 @@
+"""The chess learner, measured and run end to end (a record, not a test).
+
+  --bench   ms per train step, samples/s and the fraction of the 157.3 TF f32 MFMA
+            peak of the device step (spai_chess.ChessLearner.train_batch, upload and
+            loss read-back included) at blocks x B in --configs (default 10x32,
+            10x128, 20x32, 20x128), after warm-up; and PyTorch CPU fp32 doing the
+            same step in the same run (the reference's libtorch path), with the
+            ratio (--no-cpu skips it).  FLOPs per step: the three GEMMs (forward,
+            data gradient, weight gradient) of the 2 blocks + 1 trunk convs, each
+            2 x 64 B x 256 x 2304 (the stem counted as a full conv, the heads not
+            at all): 1.19 TFLOP at 20 blocks, B = 128.
+  --learn   spai_chess.learn() at a small configuration: the loss per iteration.
+
+Both merge their result into --out (default profiles/chess_learner/record.json).
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(REPO, "tests"), os.path.join(REPO, "oracle"), os.path.join(REPO, "self-play-ai_amd")):
+    sys.path.insert(0, p)
+
+PEAK_F32_MFMA = 157.3e12
+
+
+def step_flops(blocks, B):
+    return 3 * (2 * blocks + 1) * 2 * 64 * B * 256 * 2304
+
+
+def bench(args):
+    import chess_learner_ref as LR
+    import spai_chess as sc
+    out = {}
+    configs = [tuple(int(v) for v in c.split("x")) for c in args.configs.split(",")]
+    batches = {B: LR.make_batches(B, 1, B)[2][0] for B in sorted({B for _, B in configs})}
+    eng = sc.ChessEngine(num_searches=1, max_trees=1, max_moves=64)
+    if not args.no_cpu:
+        import torch
+        torch.set_num_threads(args.cpu_threads)
+    for blocks, B in configs:
+        x, pi, z = batches[B]
+        p0 = sc.init_params(blocks, 0)
+        L = sc.ChessLearner(eng, blocks, p0)
+        for _ in range(args.warmup):
+            L.train_batch(x, pi, z)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            loss = L.train_batch(x, pi, z)
+        dev = (time.perf_counter() - t0) / args.steps
+        L.close()
+        assert np.isfinite(loss).all()
+        fl = step_flops(blocks, B)
+        r = dict(device_ms_per_step=dev * 1e3, device_samples_per_s=B / dev, step_gflop=fl / 1e9,
+                 device_tflops=fl / dev / 1e12, fraction_of_f32_mfma_peak=fl / dev / PEAK_F32_MFMA)
+        line = (f"{blocks}x256 B={B}: device {dev * 1e3:.2f} ms/step, {B / dev:.0f} samples/s, "
+                f"{fl / dev / 1e12:.1f} TF = {fl / dev / PEAK_F32_MFMA:.3f} of the f32 MFMA peak")
+        if not args.no_cpu:
+            forward, T, _ = LR.torch_net(p0, blocks, torch.float32)
+            opt = torch.optim.Adam([t for t, _ in T if t.requires_grad], lr=1e-3)
+            tx, tpi, tz = torch.tensor(x.reshape(-1, 19, 8, 8)), torch.tensor(pi), torch.tensor(z)
+
+            def cpu_step():
+                logits, v = forward(tx)
+                l = -(torch.log_softmax(logits, 1) * tpi).sum() / B + ((v - tz) ** 2).mean()
+                opt.zero_grad()
+                l.backward()
+                opt.step()
+
+            cpu_step()
+            t0 = time.perf_counter()
+            for _ in range(args.cpu_steps):
+                cpu_step()
+            cpu = (time.perf_counter() - t0) / args.cpu_steps
+            r.update(torch_cpu_ms_per_step=cpu * 1e3, torch_cpu_samples_per_s=B / cpu, device_over_cpu=cpu / dev)
+            line += f"; torch CPU fp32 ({args.cpu_threads} threads) {cpu * 1e3:.0f} ms/step; ratio {cpu / dev:.1f}x"
+        out[f"{blocks}x{B}"] = r
+        print(line, flush=True)
+    eng.close()
+    rec = dict(steps=args.steps, warmup=args.warmup, peak_f32_mfma_tflops=PEAK_F32_MFMA / 1e12, results=out)
+    if not args.no_cpu:
+        rec.update(cpu_threads=args.cpu_threads, cpu_steps=args.cpu_steps, torch=torch.__version__)
+    return rec
+
+
+def learn(args):
+    import spai_chess as sc
+    cfg = dict(num_learn_iters=args.iters, num_self_play_iters=args.self_play_iters,
+               num_parallel_self_play_games=args.games, batch_size=args.batch, num_epochs=args.epochs,
+               num_searches=args.sims, blocks=args.blocks, seed=args.seed, clone_self_play=not args.distinct,
+               window=args.window)
+    with tempfile.TemporaryDirectory() as d:
+        t0 = time.perf_counter()
+        rec = sc.learn(checkpoint_dir=d, **cfg)
+        secs = time.perf_counter() - t0
+    for r in rec:
+        r["checkpoint"] = os.path.basename(r["checkpoint"])
+        print("iteration %d: %d samples from %d games, loss %.4f (policy %.4f, value %.4f)"
+              % (r["iteration"], r["samples"], r["games"], *r["loss"]))
+    print(f"learn: {secs:.1f} s")
+    return dict(config=cfg, seconds=secs, iterations=rec)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--bench", action="store_true")
+    ap.add_argument("--learn", action="store_true")
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "chess_learner", "record.json"))
+    ap.add_argument("--commit", default=None, help="commit hash to record (default: git rev-parse HEAD)")
+    ap.add_argument("--tag", default="", help="record under bench_<tag> / learn_<tag>")
+    ap.add_argument("--configs", default="10x32,10x128,20x32,20x128", help="--bench: blocks x B, comma separated")
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--no-cpu", action="store_true", help="--bench: skip the PyTorch CPU step")
+    ap.add_argument("--cpu-threads", type=int, default=16)
+    ap.add_argument("--cpu-steps", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--games", type=int, default=8)
+    ap.add_argument("--self-play-iters", type=int, default=2)
+    ap.add_argument("--distinct", action="store_true", help="clone_self_play=False")
+    ap.add_argument("--window", type=int, default=None, help="--learn: self-play through this many tree slots")
+    ap.add_argument("--sims", type=int, default=16)
+    ap.add_argument("--blocks", type=int, default=2)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--epochs", type=int, default=2)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    if not (args.bench or args.learn):
+        ap.error("give --bench and/or --learn")
+    commit = args.commit
+    if commit is None:
+        try:
+            commit = subprocess.run(["git", "-C", REPO, "rev-parse", "HEAD"], capture_output=True, text=True,
+                                    check=True).stdout.strip()
+        except Exception:
+            commit = "unknown"
+    record = {}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            record = json.load(f)
+    record["commit"] = commit
+    sfx = "_" + args.tag if args.tag else ""
+    if args.bench:
+        record["bench" + sfx] = bench(args)
+    if args.learn:
+        record["learn" + sfx] = learn(args)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(record, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()

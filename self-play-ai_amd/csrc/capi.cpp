@@ -106,7 +106,7 @@ extern "C" {
 
 const char *spai_last_error(void) { return g_err; }
 
-const char *spai_version(void) { return "spai 0.2 (gfx950)"; }
+const char *spai_version(void) { return "spai 0.3 (gfx950)"; }
 
 int spai_device_count(int *count) {
     PTR_CHECK(count);

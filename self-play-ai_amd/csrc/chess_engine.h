@@ -124,6 +124,7 @@ size_t net_num_params(int blocks);
 void net_init_params(int blocks, uint64_t seed, float *params);
 int net_create(spai_chess *e, int blocks, const float *params, size_t n, spai_chess_net **out);
 void net_destroy(spai_chess_net *net);
+int net_set_params(spai_chess_net *net, const float *params, size_t n);
 // evaluate `count` (device scalar) positions of x [max_n][64][kInCh] bf16
 int net_eval(spai_chess_net *net, hipStream_t st, const uint32_t *d_count, uint32_t max_n, const uint16_t *x,
              float *logits, float *value);

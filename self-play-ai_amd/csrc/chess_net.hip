@@ -594,14 +594,19 @@ void net_init_params(int blocks, uint64_t seed, float *params) {
     lin(256, 1);
 }
 
-int net_create(spai_chess *e, int blocks, const float *params, size_t n, spai_chess_net **out) {
+namespace {
+// the host image of a net: BN-folded bf16 A fragments and fp32 biases / value head
+struct Packed {
+    std::vector<uint16_t> w_stem, w_res, w_p1, w_p2;
+    std::vector<float> b_stem, b_res, b_p1, b_p2, v_w, v_b, l1_w, l1_b, l2_w, l2_b;
+};
+
+int pack_params(int blocks, const float *params, size_t n, Packed &K) {
     SPAI_CHECK(blocks >= 0 && blocks <= kMaxBlocks, SPAI_ERR_UNSUPPORTED, "chess net: 0..%d blocks (got %d)",
                kMaxBlocks, blocks);
     SPAI_CHECK(params && n == net_num_params(blocks), SPAI_ERR_INVALID, "expected %zu params, got %zu",
                net_num_params(blocks), n);
     const float *p = params;
-    std::vector<uint16_t> w_stem, w_res, w_p1, w_p2;
-    std::vector<float> b_stem, b_res, b_p1, b_p2;
     // conv + BN (eval): w' = w * g / sqrt(var + eps), b' = (b - mu) * g / sqrt(var + eps) + beta
     auto conv_bn = [&](int ci, std::vector<uint16_t> &wout, std::vector<float> &bout, int CB) {
         const float *w = p, *b = p + (size_t)kHid * ci * 9, *bn = b + kHid;
@@ -613,29 +618,38 @@ int net_create(spai_chess *e, int blocks, const float *params, size_t n, spai_ch
         }
         pack_conv(w, sc, kHid, ci, 3, CB, kCT, wout);
     };
-    conv_bn(19, w_stem, b_stem, 1);
-    for (int i = 0; i < 2 * blocks; ++i) conv_bn(kHid, w_res, b_res, 8);
+    conv_bn(19, K.w_stem, K.b_stem, 1);
+    for (int i = 0; i < 2 * blocks; ++i) conv_bn(kHid, K.w_res, K.b_res, 8);
     {
         std::vector<double> one(256, 1.0);
-        pack_conv(p, one, 256, kHid, 1, 8, kCT, w_p1);
+        pack_conv(p, one, 256, kHid, 1, 8, kCT, K.w_p1);
         p += 256 * kHid;
-        b_p1.assign(p, p + 256);
+        K.b_p1.assign(p, p + 256);
         p += 256;
-        pack_conv(p, one, 73, 256, 1, 8, kPolCT, w_p2);
+        pack_conv(p, one, 73, 256, 1, 8, kPolCT, K.w_p2);
         p += 73 * 256;
-        b_p2.assign(80, 0.f);
-        std::copy(p, p + 73, b_p2.begin());
+        K.b_p2.assign(80, 0.f);
+        std::copy(p, p + 73, K.b_p2.begin());
         p += 73;
     }
-    std::vector<float> v_w(p, p + kHid), v_b(p + kHid, p + kHid + 1);
+    K.v_w.assign(p, p + kHid);
+    K.v_b.assign(p + kHid, p + kHid + 1);
     p += kHid + 1;
-    std::vector<float> l1_w(p, p + 64 * 256), l1_b(p + 64 * 256, p + 64 * 256 + 256);
+    K.l1_w.assign(p, p + 64 * 256);
+    K.l1_b.assign(p + 64 * 256, p + 64 * 256 + 256);
     p += 64 * 256 + 256;
-    std::vector<float> l2_w(p, p + 256), l2_b(p + 256, p + 257);
+    K.l2_w.assign(p, p + 256);
+    K.l2_b.assign(p + 256, p + 257);
     p += 257;
     SPAI_CHECK((size_t)(p - params) == n, SPAI_ERR_INVALID, "parameter walk mismatch");
-    if (blocks == 0) w_res.assign(8, 0), b_res.assign(4, 0.f);   // keep the buffers non-empty
+    if (blocks == 0) K.w_res.assign(8, 0), K.b_res.assign(4, 0.f);   // keep the buffers non-empty
+    return SPAI_OK;
+}
+}  // namespace
 
+int net_create(spai_chess *e, int blocks, const float *params, size_t n, spai_chess_net **out) {
+    Packed K;
+    SPAI_TRY(pack_params(blocks, params, n, K));
     spai_chess_net *net = new spai_chess_net();
     net->eng = e;
     net->blocks = blocks;
@@ -650,25 +664,64 @@ int net_create(spai_chess *e, int blocks, const float *params, size_t n, spai_ch
         return SPAI_OK;
     };
     int rc = SPAI_OK;
-    if (rc == SPAI_OK) rc = up16(net->w_stem, w_stem);
-    if (rc == SPAI_OK) rc = up16(net->w_res, w_res);
-    if (rc == SPAI_OK) rc = up16(net->w_p1, w_p1);
-    if (rc == SPAI_OK) rc = up16(net->w_p2, w_p2);
-    if (rc == SPAI_OK) rc = upf(net->b_stem, b_stem);
-    if (rc == SPAI_OK) rc = upf(net->b_res, b_res);
-    if (rc == SPAI_OK) rc = upf(net->b_p1, b_p1);
-    if (rc == SPAI_OK) rc = upf(net->b_p2, b_p2);
-    if (rc == SPAI_OK) rc = upf(net->v_w, v_w);
-    if (rc == SPAI_OK) rc = upf(net->v_b, v_b);
-    if (rc == SPAI_OK) rc = upf(net->l1_w, l1_w);
-    if (rc == SPAI_OK) rc = upf(net->l1_b, l1_b);
-    if (rc == SPAI_OK) rc = upf(net->l2_w, l2_w);
-    if (rc == SPAI_OK) rc = upf(net->l2_b, l2_b);
+    if (rc == SPAI_OK) rc = up16(net->w_stem, K.w_stem);
+    if (rc == SPAI_OK) rc = up16(net->w_res, K.w_res);
+    if (rc == SPAI_OK) rc = up16(net->w_p1, K.w_p1);
+    if (rc == SPAI_OK) rc = up16(net->w_p2, K.w_p2);
+    if (rc == SPAI_OK) rc = upf(net->b_stem, K.b_stem);
+    if (rc == SPAI_OK) rc = upf(net->b_res, K.b_res);
+    if (rc == SPAI_OK) rc = upf(net->b_p1, K.b_p1);
+    if (rc == SPAI_OK) rc = upf(net->b_p2, K.b_p2);
+    if (rc == SPAI_OK) rc = upf(net->v_w, K.v_w);
+    if (rc == SPAI_OK) rc = upf(net->v_b, K.v_b);
+    if (rc == SPAI_OK) rc = upf(net->l1_w, K.l1_w);
+    if (rc == SPAI_OK) rc = upf(net->l1_b, K.l1_b);
+    if (rc == SPAI_OK) rc = upf(net->l2_w, K.l2_w);
+    if (rc == SPAI_OK) rc = upf(net->l2_b, K.l2_b);
     if (rc != SPAI_OK) {
         net_destroy(net);
         return rc;
     }
     *out = net;
+    return SPAI_OK;
+}
+
+// weight refresh in place: net_create's host fold and pack written into the net's own
+// allocations, stream-ordered behind whatever search still reads the old weights
+int net_set_params(spai_chess_net *net, const float *params, size_t n) {
+    SPAI_CHECK(params && n == net_num_params(net->blocks), SPAI_ERR_INVALID, "expected %zu params, got %zu",
+               net_num_params(net->blocks), n);
+    Packed K;
+    SPAI_TRY(pack_params(net->blocks, params, n, K));
+    hipStream_t st = net->eng->stream;
+    auto put16 = [&](DevBuf<uint16_t> &d, const std::vector<uint16_t> &h) -> int {
+        SPAI_CHECK(d.n == h.size(), SPAI_ERR_INVALID, "net allocation does not match");
+        SPAI_HIP(hipMemcpyAsync(d.p, h.data(), h.size() * 2, hipMemcpyHostToDevice, st));
+        return SPAI_OK;
+    };
+    auto putf = [&](DevBuf<float> &d, const std::vector<float> &h) -> int {
+        SPAI_CHECK(d.n == h.size(), SPAI_ERR_INVALID, "net allocation does not match");
+        SPAI_HIP(hipMemcpyAsync(d.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));
+        return SPAI_OK;
+    };
+    int rc = SPAI_OK;
+    if (rc == SPAI_OK) rc = put16(net->w_stem, K.w_stem);
+    if (rc == SPAI_OK) rc = put16(net->w_res, K.w_res);
+    if (rc == SPAI_OK) rc = put16(net->w_p1, K.w_p1);
+    if (rc == SPAI_OK) rc = put16(net->w_p2, K.w_p2);
+    if (rc == SPAI_OK) rc = putf(net->b_stem, K.b_stem);
+    if (rc == SPAI_OK) rc = putf(net->b_res, K.b_res);
+    if (rc == SPAI_OK) rc = putf(net->b_p1, K.b_p1);
+    if (rc == SPAI_OK) rc = putf(net->b_p2, K.b_p2);
+    if (rc == SPAI_OK) rc = putf(net->v_w, K.v_w);
+    if (rc == SPAI_OK) rc = putf(net->v_b, K.v_b);
+    if (rc == SPAI_OK) rc = putf(net->l1_w, K.l1_w);
+    if (rc == SPAI_OK) rc = putf(net->l1_b, K.l1_b);
+    if (rc == SPAI_OK) rc = putf(net->l2_w, K.l2_w);
+    if (rc == SPAI_OK) rc = putf(net->l2_b, K.l2_b);
+    const hipError_t se = hipStreamSynchronize(st);   // the host vectors die here
+    SPAI_TRY(rc);
+    SPAI_HIP(se);
     return SPAI_OK;
 }
 

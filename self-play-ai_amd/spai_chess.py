@@ -6,6 +6,8 @@ Mirrors the reference's chess surface (joshua16266261/self-play-ai):
   Net (model/chess.rs)             -> ChessNet.forward
   Tree + Mcts::search (mcts.rs)    -> ChessEngine.trees_create / search / use_subtree
   SelfPlayWorker::self_play        -> ChessEngine.self_play
+  Model::train (model/mod.rs)      -> ChessLearner.train_batch / train
+  Learner::learn (learner.rs)      -> learn
 Every call goes through the HIP library; there is no CPU fallback.
 """
 import ctypes as C
@@ -13,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 import spai
-from spai import EVAL_HASH, EVAL_NET, EVAL_UNIFORM, Config, SelfPlayStats, SpaiError  # noqa: F401
+from spai import EVAL_HASH, EVAL_NET, EVAL_UNIFORM, GAME_CHESS, Config, SelfPlayStats, SpaiError  # noqa: F401
 
 POLICY, ENC, MAX_MOVES = 4672, 1216, 256
 
@@ -66,6 +68,15 @@ def lib():
         L.spai_chess_selfplay_stream.argtypes = [vp, u32, u32, u64, SINK, vp, P(SelfPlayStats)]
         L.spai_chess_set_timing.argtypes = [vp, i32]
         L.spai_chess_timing.argtypes = [vp, vp, vp, vp]
+        L.spai_chess_net_set_params.argtypes = [vp, vp, C.c_size_t]
+        L.spai_chess_learner_create.argtypes = [vp, i32, vp, C.c_size_t, P(spai.AdamConfig), P(vp)]
+        L.spai_chess_learner_destroy.argtypes = [vp]
+        L.spai_chess_learner_train_batch.argtypes = [vp, u32, vp, vp, vp, vp]
+        L.spai_chess_learner_train.argtypes = [vp, u32, vp, vp, vp, u32, u32, u64, vp]
+        L.spai_chess_learner_params.argtypes = [vp, vp, C.c_size_t]
+        L.spai_chess_learner_grads.argtypes = [vp, vp, C.c_size_t]
+        L.spai_chess_learner_activation.argtypes = [vp, i32, vp, C.c_size_t]
+        L.spai_chess_learner_last_batch.argtypes = [vp, P(u32)]
         _ready = True
     return L
 
@@ -308,3 +319,147 @@ class ChessNet:
         v = np.zeros(n, np.float32)
         _check(lib().spai_chess_predict(self.h, first, n, _p(pr), _p(v)))
         return pr, v
+
+    def set_params(self, params):
+        """weight refresh in place: forward afterwards is bit-identical to a fresh
+        ChessNet of the same parameters"""
+        p = np.ascontiguousarray(params, np.float32)
+        _check(lib().spai_chess_net_set_params(self.h, _p(p), p.size))
+
+
+class ChessLearner:
+    """Device train step of the chess net (model/chess.rs under
+    model/mod.rs:128-141) on the engine's device and stream, in exact fp32:
+    train-mode forward, policy NLL + value MSE, backward, one Adam step.
+    Mirrors spai_ttt.TTTLearner."""
+
+    def __init__(self, engine, blocks, params, **adam):
+        cfg = spai.AdamConfig()
+        _check(lib().spai_adam_config_default(C.byref(cfg)))
+        for k, v in adam.items():
+            setattr(cfg, k, float(v))
+        p = np.ascontiguousarray(params, np.float32)
+        self.n, self.blocks = p.size, blocks
+        self.eng = engine   # the learner runs on the engine's stream: keep it alive
+        h = C.c_void_p()
+        _check(lib().spai_chess_learner_create(engine.h, blocks, _p(p), p.size, C.byref(cfg), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().spai_chess_learner_destroy(self.h)
+            self.h = None
+
+    @staticmethod
+    def _batch(states, policies, values):
+        x = np.ascontiguousarray(states, np.float32).reshape(-1, ENC)
+        pi = np.ascontiguousarray(policies, np.float32).reshape(-1, POLICY)
+        z = np.ascontiguousarray(values, np.float32).reshape(-1)
+        assert len(x) == len(pi) == len(z)
+        return x, pi, z
+
+    def train_batch(self, states, policies, values):
+        x, pi, z = self._batch(states, policies, values)
+        loss = np.zeros(3, np.float32)
+        _check(lib().spai_chess_learner_train_batch(self.h, len(z), _p(x), _p(pi), _p(z), _p(loss)))
+        return loss   # total, policy, value
+
+    def train(self, states, policies, values, epochs=1, batch=32, seed=0):
+        """Model::train (model/mod.rs:100-149): fresh Adam, one permutation, epochs x batches"""
+        x, pi, z = self._batch(states, policies, values)
+        loss = np.zeros(3, np.float32)
+        _check(lib().spai_chess_learner_train(self.h, len(z), _p(x), _p(pi), _p(z), epochs, batch, seed, _p(loss)))
+        return loss
+
+    def last_batch(self):
+        """the batch size of the latest train step (after train(): the last minibatch's)"""
+        n = C.c_uint32()
+        _check(lib().spai_chess_learner_last_batch(self.h, C.byref(n)))
+        return n.value
+
+    def params(self):
+        out = np.zeros(self.n, np.float32)
+        _check(lib().spai_chess_learner_params(self.h, _p(out), self.n))
+        return out
+
+    def grads(self):
+        out = np.zeros(self.n, np.float32)
+        _check(lib().spai_chess_learner_grads(self.h, _p(out), self.n))
+        return out
+
+    def activation(self, layer):
+        """the last train step's post-ReLU activations: layers 0 .. 2*blocks the trunk
+        convs and 2*blocks+1 the first policy conv, [B][256][8][8]; 2*blocks+2 the value
+        conv, [B][64]; 2*blocks+3 the first value linear, [B][256]"""
+        nt, B = 2 * self.blocks + 1, self.last_batch()
+        shape = (B, 256, 8, 8) if layer <= nt else (B, 64) if layer == nt + 1 else (B, 256)
+        out = np.zeros(shape, np.float32)
+        _check(lib().spai_chess_learner_activation(self.h, layer, _p(out), out.size))
+        return out
+
+
+def _samples(games):
+    """self-play games (ascending game id) -> states [n][1216], policies [n][4672], values [n]"""
+    games = sorted(games, key=lambda g: g["game"])
+    return (np.concatenate([g["enc"] for g in games]), np.concatenate([g["policy"] for g in games]),
+            np.concatenate([g["value"] for g in games]))
+
+
+def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_games=100, batch_size=32, num_epochs=4,
+          num_searches=600, temperature=1.25, c=2.0, blocks=10, seed=0, checkpoint_dir=".", clone_self_play=True,
+          params=None, device=0, on_train_set=None, window=None, max_moves=None):
+    """Learner::learn (learner.rs:98-196) for chess, with mcts.rs:46-59's defaults:
+    per iteration i, self-play with the current weights on one ChessEngine (the net
+    refreshed in place), Model::train on the samples, checkpoint i.safetensors.
+
+    clone_self_play (the reference's behaviour, learner.rs:127-137: the self-play
+    state is cloned into every self-play iteration, so all of them play the same
+    games): one batch of num_parallel_self_play_games games, its samples repeated
+    num_self_play_iters times.  False: num_self_play_iters distinct batches.  Game
+    ids (the sampling streams) are disjoint across batches and learn iterations.
+    window: play each batch through that many tree slots (ChessEngine.self_play).
+    on_train_set(i, states, policies, values, game_ids) sees every training set.
+    Returns per-iteration records: samples, loss [total, policy, value] of the last
+    step, games, checkpoint."""
+    import os
+    P = np.ascontiguousarray(init_params(blocks, seed) if params is None else params, np.float32)
+    G = num_parallel_self_play_games
+    eng = ChessEngine(num_searches=num_searches, max_trees=G if window is None else int(window), eval_kind=EVAL_NET,
+                      device=device, c=c, temperature=temperature, seed=seed, max_moves=max_moves)
+    net = ChessNet(eng, blocks, P)
+    eng.set_net(net)
+    L = ChessLearner(eng, blocks, P)
+    os.makedirs(checkpoint_dir, exist_ok=True)
+    out = []
+    try:
+        for i in range(num_learn_iters):
+            if i:
+                net.set_params(L.params())
+            batches = 1 if clone_self_play else num_self_play_iters
+            parts, gids, n_games = [], [], 0
+            for b in range(batches):
+                base = (i * num_self_play_iters + b) * G
+                games, _ = eng.self_play(G, game_id_base=base, window=window)
+                n_games += len(games)
+                parts.append(_samples(games))
+                gids.append(np.concatenate([np.full(g["n"], g["game"], np.int64)
+                                            for g in sorted(games, key=lambda g: g["game"])]))
+            if clone_self_play:
+                parts, gids = parts * num_self_play_iters, gids * num_self_play_iters
+            s, p, v = (np.concatenate([q[k] for q in parts]) for k in range(3))
+            if on_train_set is not None:
+                on_train_set(i, s, p, v, np.concatenate(gids))
+            loss = L.train(s, p, v, epochs=num_epochs, batch=batch_size, seed=_iter_seed(seed, i))
+            path = os.path.join(checkpoint_dir, f"{i}.safetensors")
+            spai.save_params(path, L.params(), blocks, 256, game=GAME_CHESS)   # spai_params_save_safetensors
+            out.append(dict(iteration=i, samples=int(len(v)), loss=[float(x) for x in loss], games=n_games,
+                            checkpoint=path))
+    finally:
+        L.close()
+        eng.close()
+    return out
+
+
+def _iter_seed(seed, i):
+    """the training permutation's seed of learn iteration i"""
+    return (int(seed) * 0x9E3779B97F4A7C15 + i + 1) & 0xFFFFFFFFFFFFFFFF
