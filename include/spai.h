@@ -663,6 +663,90 @@ int spai_chess_learner_grads(spai_chess_learner *l, float *grads, size_t n_param
 int spai_chess_learner_activation(spai_chess_learner *l, int layer, float *out, size_t n);
 int spai_chess_learner_last_batch(spai_chess_learner *l, uint32_t *n);
 
+/* ------------------------------------------------------------ chess match
+ * play() (main.rs:54-135, whose commented-out lines are the chess variant) with
+ * a second evaluator in the human's seat, over n_games chess games at once: the
+ * chess form of spai_match_run ("match" above), in its wording where the games
+ * allow it.
+ *   Game g has id game_id_base + g and belongs to pair id / 2; player A moves
+ * first (plays the first searched ply) when the id is even, B when it is odd.
+ * Both games of a pair start from the same position: cfg.start[pair -
+ * game_id_base / 2] when start is given (loaded with an empty transposition
+ * table, as by spai_chess_games_write), otherwise State::default(), and then
+ * opening_plies plies played from it: ply k plays the idx-th move of the
+ * position's legal list in MoveGen order, idx = min((int)(u * (float)n_legal),
+ * n_legal - 1) with u the 23-bit Philox uniform of (cfg.seed, pair, k) (the
+ * uniform of self-play's move draw).  The opening's positions enter the game's
+ * repetition history like any played move.
+ *   Every game has one tree per player, both Tree::with_root_state of the
+ * position after the opening, history included.  The side to move searches its
+ * own tree with its own evaluator for its own num_searches iterations, plays the
+ * most-visited root child (ties: the last) and re-roots its tree there
+ * (use_subtree: the root keeps N and W, the old root's list hash joins the
+ * tree's history).  The opponent's tree follows the move: advanced to the child
+ * carrying that move code when its root is expanded (the same child index, both
+ * roots being the same position), otherwise (only before the second player's
+ * first search) a fresh one-node tree at the new position with the mover's
+ * history.  After the step both trees agree on root board, repetition count and
+ * history.  A game ends on Won (the mover wins) or Tied.  Adjudication: a game
+ * whose n_moves reaches max_plies (0 = no limit) while still Ongoing ends as a
+ * draw with adjudicated = 1.  moves receives the first min(n_moves,
+ * moves_stride) move codes of each game.  All the A-to-move trees of a ply run
+ * as one search chain and all the B-to-move trees as the other, side by side on
+ * two streams.
+ *   The engine's own cfg.eval, net, temperature and timers are neither used nor
+ * changed; its trees are replaced, as spai_chess_selfplay_run replaces them.
+ * SPAI_ERR_INVALID: start != NULL together with opening_plies != 0; a start
+ * position that is not Ongoing, or without exactly one king per side (the rule
+ * of spai_chess_games_write); a struct_size other than
+ * sizeof(spai_chess_match_config); opening_plies > 3; 2 * n_games > cfg.max_trees;
+ * num_searches outside 1..cfg.num_searches; NET with a null net or a net of
+ * another engine; moves != NULL with moves_stride == 0.  Memory: a tree takes
+ * 2 * cap * 28 B with cap = max(4 * cfg.num_searches * 218, 16384), plus
+ * cfg.max_moves * 8 B of history: about 19.5 MB per tree at 400 simulations,
+ * and a game holds two.  A NaN UCB or a root without a visited child
+ * (num_searches = 1) is SPAI_ERR_NAN, as in self-play; arena, depth and history
+ * overflows are SPAI_ERR_CAPACITY.  Every return leaves the engine idle and
+ * usable. */
+typedef struct spai_chess_match_player {
+    int32_t eval;              /* spai_eval: NET, UNIFORM or HASH */
+    uint32_t num_searches;     /* simulations per move, 1..cfg.num_searches */
+    spai_chess_net *net;       /* SPAI_EVAL_NET: this player's net; else ignored */
+} spai_chess_match_player;
+typedef struct spai_chess_match_config {
+    uint32_t struct_size;      /* sizeof(spai_chess_match_config) */
+    uint32_t opening_plies;    /* 0..3 (no chess game ends before ply 4); default 2 */
+    uint32_t max_plies;        /* 0 = none; see "adjudication"; default 512 */
+    uint32_t moves_stride;     /* uint16 entries per game in `moves` (0 if moves == NULL) */
+    uint64_t seed;             /* the openings' Philox key */
+    const spai_chess_state *start;   /* NULL, or one start position per pair */
+} spai_chess_match_config;
+typedef struct spai_chess_match_game {
+    uint64_t game_id;
+    int8_t a_moves_first, result_a;   /* +1 A won, 0 draw, -1 B won */
+    uint8_t status;                   /* spai_status of the final position (ONGOING iff adjudicated) */
+    uint8_t adjudicated;
+    uint32_t n_moves;                 /* plies played, the opening's included */
+} spai_chess_match_game;
+typedef struct spai_chess_match_stats {
+    double a_wins[2], draws[2], b_wins[2];   /* [0] games A moved first, [1] B moved first */
+    double sims[2], evals[2];                /* per player: trees x iterations, leaves evaluated */
+    double adjudicated, plies, seconds;
+} spai_chess_match_stats;
+/* struct_size set, opening_plies 2, max_plies 512, moves_stride 0, seed 0, start NULL */
+int spai_chess_match_config_default(spai_chess_match_config *cfg);
+int spai_chess_match_run(spai_chess *e, const spai_chess_match_player *a, const spai_chess_match_player *b,
+                         uint32_t n_games, uint64_t game_id_base, const spai_chess_match_config *cfg,
+                         spai_chess_match_game *games /* [n_games] or NULL */,
+                         uint16_t *moves /* [n_games][moves_stride] or NULL */,
+                         spai_chess_match_stats *stats /* or NULL */);
+/* Measurement only: on != 0 runs both chains of later matches in order on the
+ * engine's stream instead of side by side on two (the default).  Results are the same. */
+int spai_chess_match_set_one_stream(spai_chess *e, int on);
+/* root children of a tree without searching it (n = 0: root not expanded):
+ * moves / visits [SPAI_CHESS_MAX_MOVES], zero past n; any output may be NULL */
+int spai_chess_tree_children(spai_chess *e, uint32_t tree, uint16_t *moves, uint32_t *visits, uint32_t *n);
+
 
 /* ---------------------------------------------------------------- tictactoe
  * game/tictactoe.rs + model/tictactoe.rs (BASELINE config 1) on the device.

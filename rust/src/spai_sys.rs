@@ -142,6 +142,50 @@ pub struct spai_match_stats {
     pub evals: [f64; 2],
     pub seconds: f64,
 }
+
+// play() (main.rs:54-135, the chess variant) between two evaluators: spai_chess_match_run
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct spai_chess_match_player {
+    pub eval: i32,
+    pub num_searches: u32,
+    pub net: *mut spai_chess_net,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct spai_chess_match_config {
+    pub struct_size: u32,
+    pub opening_plies: u32,
+    pub max_plies: u32,
+    pub moves_stride: u32,
+    pub seed: u64,
+    pub start: *const spai_chess_state,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct spai_chess_match_game {
+    pub game_id: u64,
+    pub a_moves_first: i8,
+    pub result_a: i8,
+    pub status: u8,
+    pub adjudicated: u8,
+    pub n_moves: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct spai_chess_match_stats {
+    pub a_wins: [f64; 2],
+    pub draws: [f64; 2],
+    pub b_wins: [f64; 2],
+    pub sims: [f64; 2],
+    pub evals: [f64; 2],
+    pub adjudicated: f64,
+    pub plies: f64,
+    pub seconds: f64,
+}
 pub enum spai_learner {}
 pub enum spai_ttt {}
 pub enum spai_ttt_net {}
@@ -225,6 +269,14 @@ extern "C" {
                              child_ids: *mut u32, child_visits: *mut f32, child_moves: *mut u16,
                              n_children: *mut u32) -> c_int;
     pub fn spai_chess_tree_use_subtree(e: *mut spai_chess, tree: u32, child_index: u32) -> c_int;
+    pub fn spai_chess_tree_children(e: *mut spai_chess, tree: u32, moves: *mut u16, visits: *mut u32,
+                                    n: *mut u32) -> c_int;
+    pub fn spai_chess_match_set_one_stream(e: *mut spai_chess, on: c_int) -> c_int;
+    pub fn spai_chess_match_config_default(cfg: *mut spai_chess_match_config) -> c_int;
+    pub fn spai_chess_match_run(e: *mut spai_chess, a: *const spai_chess_match_player,
+                                b: *const spai_chess_match_player, n_games: u32, game_id_base: u64,
+                                cfg: *const spai_chess_match_config, games: *mut spai_chess_match_game,
+                                moves: *mut u16, stats: *mut spai_chess_match_stats) -> c_int;
 
     // Policy trait helpers on a flat policy (game/mod.rs:35-44)
     pub fn spai_policy_normalize(p: *mut f32, n: u32) -> c_int;

@@ -70,6 +70,7 @@ void release_all(spai_chess *e) {
     B.value.release();
     e->active.release();
     e->err.release();
+    match_release(e);
     for (hipEvent_t ev : e->timer.ev) (void)hipEventDestroy(ev);
     e->timer.ev.clear();
 }
@@ -325,6 +326,51 @@ int spai_chess_selfplay_stream(spai_chess *e, uint32_t n_games, uint32_t window,
         return SPAI_ERR_INVALID;
     }
     return selfplay_run(e, n_games, game_id_base, sink, user, stats, window);
+}
+
+int spai_chess_tree_children(spai_chess *e, uint32_t tree, uint16_t *moves, uint32_t *visits, uint32_t *n) {
+    CH_CHECK(e);
+    return tree_children(e, tree, moves, visits, n);
+}
+
+int spai_chess_match_set_one_stream(spai_chess *e, int on) {
+    CH_CHECK(e);
+    return match_set_one_stream(e, on);
+}
+
+int spai_chess_match_config_default(spai_chess_match_config *cfg) {
+    CH_PTR(cfg);
+    *cfg = spai_chess_match_config{};
+    cfg->struct_size = (uint32_t)sizeof(spai_chess_match_config);
+    cfg->opening_plies = 2;
+    cfg->max_plies = 512;
+    return SPAI_OK;
+}
+
+int spai_chess_match_run(spai_chess *e, const spai_chess_match_player *a, const spai_chess_match_player *b,
+                         uint32_t n_games, uint64_t gid_base, const spai_chess_match_config *cfg,
+                         spai_chess_match_game *games, uint16_t *moves, spai_chess_match_stats *stats) {
+    CH_CHECK(e);
+    CH_PTR(a);
+    CH_PTR(b);
+    CH_PTR(cfg);
+    SPAI_CHECK(cfg->struct_size == sizeof(spai_chess_match_config), SPAI_ERR_INVALID,
+               "spai_chess_match_config.struct_size %u, expected %zu", cfg->struct_size,
+               sizeof(spai_chess_match_config));
+    SPAI_CHECK(cfg->opening_plies <= 3, SPAI_ERR_INVALID, "opening_plies %u > 3", cfg->opening_plies);
+    SPAI_CHECK(!cfg->start || cfg->opening_plies == 0, SPAI_ERR_INVALID,
+               "start positions take no opening (opening_plies %u)", cfg->opening_plies);
+    SPAI_CHECK(!moves || cfg->moves_stride > 0, SPAI_ERR_INVALID, "moves given with moves_stride 0");
+    SPAI_CHECK(n_games > 0 && 2 * (uint64_t)n_games <= e->cfg.max_trees, SPAI_ERR_INVALID,
+               "a match of %u games needs %llu trees, max_trees=%u", n_games, 2ull * n_games, e->cfg.max_trees);
+    for (const spai_chess_match_player *p : {a, b}) {
+        SPAI_CHECK(p->eval >= SPAI_EVAL_NET && p->eval <= SPAI_EVAL_HASH, SPAI_ERR_INVALID, "bad eval kind %d", p->eval);
+        SPAI_CHECK(p->eval != SPAI_EVAL_NET || p->net, SPAI_ERR_INVALID, "player with eval = NET but no net");
+        SPAI_CHECK(p->eval != SPAI_EVAL_NET || p->net->eng == e, SPAI_ERR_INVALID, "net belongs to another engine");
+        SPAI_CHECK(p->num_searches >= 1 && p->num_searches <= e->cfg.num_searches, SPAI_ERR_INVALID,
+                   "player num_searches %u not in [1, cfg.num_searches=%u]", p->num_searches, e->cfg.num_searches);
+    }
+    return match_run(e, a, b, n_games, gid_base, cfg, games, moves, stats);
 }
 
 int spai_chess_set_timing(spai_chess *e, int enabled) {

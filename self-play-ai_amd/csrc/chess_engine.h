@@ -52,6 +52,24 @@ struct Batch {
     DevBuf<float> value;        // [cap]
 };
 
+// spai_chess_match_run's own buffers (chess_match.hip): player B's chain (A's is the
+// engine's), the ply's tree lists and move records, the start positions.  What the
+// host exchanges with the device per ply lives in pinned memory (h_*), so the copies
+// are asynchronous and enqueueing one chain never waits for the other.
+struct MatchBufs {
+    hipStream_t stream = nullptr;       // chain B
+    bool one_stream = false;            // measurement: chain B on the engine's stream too
+    uint32_t cap = 0;                   // games the buffers below hold
+    Batch batch;                        // chain B's leaf batch
+    DevBuf<uint32_t> active, err;       // chain B's tree list and error word
+    DevBuf<uint4> rec[2];               // [chain][game of the ply] move records
+    DevBuf<uint4> start_rec;            // [game] record of k_cmatch_start
+    DevBuf<Board> start;                // [pair] start positions (cfg.start)
+    uint32_t *h_list[2] = {nullptr, nullptr};   // pinned [chain][cap]: the ply's trees
+    uint4 *h_rec[2] = {nullptr, nullptr};       // pinned [chain][cap]: the ply's move records
+    uint4 *h_srec = nullptr;                    // pinned [cap]: k_cmatch_start's records
+};
+
 // rules API game slots
 struct Slots {
     uint32_t n = 0, max_hist = 0;
@@ -82,6 +100,7 @@ struct spai_chess {
     spai::DevBuf<uint32_t> err;      // device error flags
     spai_chess_net *net = nullptr;
     spai::KernelTimer timer;
+    spai::chess::MatchBufs match;
 };
 
 struct spai_chess_net {
@@ -138,9 +157,17 @@ int search(spai_chess *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_sea
 int tree_use_subtree(spai_chess *e, uint32_t tree, uint32_t child_index);
 int tree_reset_from_slot(spai_chess *e, uint32_t tree, uint32_t slot);
 int tree_root(spai_chess *e, uint32_t tree, spai_chess_state *root, uint32_t *visits, float *value_sum);
+// moves / visits [kMaxMoves] (zero past *n), any of them null
+int tree_children(spai_chess *e, uint32_t tree, uint16_t *moves, uint32_t *visits, uint32_t *n);
 int trees_advance(spai_chess *e, uint32_t n, const uint32_t *tree_idx, const uint32_t *child_index, uint8_t *status,
                   uint32_t *reps);
 int selfplay_run(spai_chess *e, uint32_t n_games, uint64_t gid_base, spai_chess_sample_sink sink, void *user,
                  spai_selfplay_stats *stats, uint32_t window = 0);
+// chess_match.hip
+int match_run(spai_chess *e, const spai_chess_match_player *a, const spai_chess_match_player *b, uint32_t n_games,
+              uint64_t gid_base, const spai_chess_match_config *cfg, spai_chess_match_game *games, uint16_t *moves,
+              spai_chess_match_stats *stats);
+void match_release(spai_chess *e);
+int match_set_one_stream(spai_chess *e, int on);
 }  // namespace chess
 }  // namespace spai

@@ -23,43 +23,18 @@
 #include <cmath>
 #include <cstring>
 
-#include "chess_engine.h"
+#include "chess_search_internal.h"
 #include "philox.h"
 
 namespace spai {
 namespace chess {
 namespace {
 
-constexpr int kWavesPerBlock = 4;
-constexpr uint32_t kErrNan = 1, kErrDepth = 2, kErrCap = 4, kErrHist = 8;
-constexpr int kMaxChildren = 218;   // most legal moves of any chess position
-
-struct TV {
-    uint4 *nodes;
-    uint32_t *first;
-    uint64_t *nhash;
-    uint32_t *root, *fill, *half;
-    Board *root_board;
-    uint32_t *root_reps;
-    uint64_t *hist;
-    uint32_t *hist_n;
-    uint32_t max_hist;
-    uint32_t *path, *depth;
-    uint16_t *leaf_moves;
-    uint32_t *leaf_n;
-    uint64_t *leaf_hash, *leaf_key;
-    uint32_t cap;
-};
-
 struct BV {
     uint32_t *tree;
     uint16_t *x;
     float *logits, *value;
 };
-
-__device__ __forceinline__ size_t tbase(const TV &T, uint32_t t) {
-    return (size_t)t * 2 * T.cap + (size_t)T.half[t] * T.cap;
-}
 
 // mcts.rs:91-100 in the reference's operation order (-ffp-contract=off)
 __device__ __forceinline__ float ucb(float sq_parent, const uint4 &ch, float c) {
@@ -445,38 +420,16 @@ __global__ void k_cadvance(TV T, const uint32_t *__restrict__ active, uint32_t n
     const uint32_t gi = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     if (gi >= n_active) return;
     const uint32_t t = active[gi];
-    const size_t base = tbase(T, t);
-    const uint32_t r = T.root[t];
-    const uint32_t child = T.first[base + r] + pick[gi];
-    Board b = T.root_board[t];
-    const uint64_t rh = T.nhash[base + r];
-    const uint32_t hn = T.hist_n[t];
-    if (hn >= T.max_hist) {
-        if (lane == 0) atomicOr(err, kErrHist);
-        return;
-    }
-    apply_move(b, (int)(T.nodes[base + child].w & 0xFFFFu));
-    const GenOut g = wave_movegen(b, nullptr, lane);
-    const uint64_t *hist = T.hist + (size_t)t * T.max_hist;
-    uint32_t hits = lane == 0 && rh == g.hash ? 1u : 0u;
-    for (uint32_t i = lane; i < hn; i += 64) hits += hist[i] == g.hash;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) hits += __shfl_xor(hits, o, 64);
-    const uint32_t reps = 1 + hits;
-    int status = SPAI_ONGOING;
-    if (g.n == 0) status = g.in_check ? SPAI_WON : SPAI_TIED;
-    else if (reps >= 3 || b.fifty >= 100) status = SPAI_TIED;
-    b.status = (uint8_t)status;
+    Board b;
+    uint32_t reps;
+    if (!advance_step(T, t, pick[gi], lane, err, b, reps)) return;
     if (lane == 0) {
-        T.hist[(size_t)t * T.max_hist + hn] = rh;
-        T.hist_n[t] = hn + 1;
-        T.root[t] = child;
-        T.root_board[t] = b;
-        T.root_reps[t] = reps;
-        out[gi] = (uint32_t)status | (reps << 8);
+        out[gi] = (uint32_t)b.status | (reps << 8);
         boards[gi] = b;
     }
 }
+
+}  // namespace
 
 TV view(spai_chess *e) {
     Trees &Tr = e->trees;
@@ -502,23 +455,19 @@ TV view(spai_chess *e) {
     return T;
 }
 
-BV bview(spai_chess *e) {
+namespace {
+BV bview(const Batch &b) {
     BV B;
-    B.tree = e->batch.tree.p;
-    B.x = e->batch.x.p;
-    B.logits = e->batch.logits.p;
-    B.value = e->batch.value.p;
+    B.tree = b.tree.p;
+    B.x = b.x.p;
+    B.logits = b.logits.p;
+    B.value = b.value.p;
     return B;
 }
+}  // namespace
 
-uint32_t blocks_for(uint32_t n) { return (n + kWavesPerBlock - 1) / kWavesPerBlock; }
-
-int check_err(spai_chess *e) {
-    uint32_t f = 0;
-    SPAI_HIP(hipMemcpyAsync(&f, e->err.p, 4, hipMemcpyDeviceToHost, e->stream));
-    SPAI_HIP(hipStreamSynchronize(e->stream));
+int err_code(spai_chess *e, uint32_t f) {
     if (!f) return SPAI_OK;
-    SPAI_HIP(hipMemsetAsync(e->err.p, 0, 4, e->stream));
     if (f & kErrNan) {
         set_error("NaN UCB score (the reference panics in partial_cmp().unwrap(), mcts.rs:106-109)");
         return SPAI_ERR_NAN;
@@ -535,13 +484,15 @@ int check_err(spai_chess *e) {
     return SPAI_ERR_CAPACITY;
 }
 
-// timing: sampled launches bracketed by events on the engine stream
-struct Timing {
-    std::vector<hipEvent_t> ev;
-    std::vector<int> which;
-    size_t used = 0;
-};
-
+namespace {
+int check_err(spai_chess *e) {
+    uint32_t f = 0;
+    SPAI_HIP(hipMemcpyAsync(&f, e->err.p, 4, hipMemcpyDeviceToHost, e->stream));
+    SPAI_HIP(hipStreamSynchronize(e->stream));
+    if (!f) return SPAI_OK;
+    SPAI_HIP(hipMemsetAsync(e->err.p, 0, 4, e->stream));
+    return err_code(e, f);
+}
 }  // namespace
 
 int trees_create(spai_chess *e, uint32_t n) {
@@ -590,74 +541,108 @@ int trees_create(spai_chess *e, uint32_t n) {
     return SPAI_OK;
 }
 
-namespace {
-int run_search(spai_chess *e, uint32_t na, uint32_t sims, double *evals_out) {
-    Trees &Tr = e->trees;
-    Batch &B = e->batch;
+Chain engine_chain(spai_chess *e, uint32_t n, uint32_t sims) {
+    Chain C;
+    C.stream = e->stream;
+    C.active = e->active.p;
+    C.n = n;
+    C.batch = &e->batch;
+    C.err = e->err.p;
+    C.kind = (int)e->cfg.eval;
+    C.net = e->net;
+    C.sims = sims;
+    C.timer = &e->timer;
+    return C;
+}
+
+int chain_launch(spai_chess *e, const Chain &C) {
+    if (!C.n) return SPAI_OK;
+    Batch &B = *C.batch;
+    const uint32_t na = C.n, sims = C.sims;
+    SPAI_CHECK(B.cap >= na, SPAI_ERR_INVALID, "internal: leaf batch of %u slots for %u trees", B.cap, na);
     if (B.counts.n < sims) SPAI_TRY(B.counts.alloc(sims));
-    SPAI_HIP(hipMemsetAsync(B.counts.p, 0, sizeof(uint32_t) * sims, e->stream));
+    SPAI_HIP(hipMemsetAsync(B.counts.p, 0, sizeof(uint32_t) * sims, C.stream));
     const TV T = view(e);
-    const BV BVv = bview(e);
-    const int kind = (int)e->cfg.eval;
-    SPAI_CHECK(kind != SPAI_EVAL_NET || e->net, SPAI_ERR_INVALID, "cfg.eval = NET but no net set (spai_chess_set_net)");
-    k_ccompact<<<blocks_for(na), 64 * kWavesPerBlock, 0, e->stream>>>(T, e->active.p, na, sims * kMaxChildren,
-                                                                      e->err.p);
+    const BV BVv = bview(B);
+    const int kind = C.kind;
+    SPAI_CHECK(kind != SPAI_EVAL_NET || C.net, SPAI_ERR_INVALID, "cfg.eval = NET but no net set (spai_chess_set_net)");
+    k_ccompact<<<blocks_for(na), 64 * kWavesPerBlock, 0, C.stream>>>(T, C.active, na, sims * kMaxChildren, C.err);
     SPAI_HIP(hipGetLastError());
-    KernelTimer &tm = e->timer;
+    KernelTimer *tm = C.timer;
     auto stamp = [&](int which, bool begin) -> int {
-        if (tm.used >= tm.ev.size()) {
+        if (tm->used >= tm->ev.size()) {
             hipEvent_t ev;
             SPAI_HIP(hipEventCreate(&ev));
-            tm.ev.push_back(ev);
+            tm->ev.push_back(ev);
         }
-        SPAI_HIP(hipEventRecord(tm.ev[tm.used++], e->stream));
-        if (begin) tm.which.push_back(which);
+        SPAI_HIP(hipEventRecord(tm->ev[tm->used++], C.stream));
+        if (begin) tm->which.push_back(which);
         return SPAI_OK;
     };
     for (uint32_t it = 0; it < sims; ++it) {
-        const bool timed = tm.enabled && (it % 8 == 0);
+        const bool timed = tm && tm->enabled && (it % 8 == 0);
         uint32_t *cnt = B.counts.p + it;
         if (timed) SPAI_TRY(stamp(0, true));
-        k_cleaf<<<blocks_for(na), 64 * kWavesPerBlock, 0, e->stream>>>(T, BVv, e->active.p, na, e->cfg.c, cnt,
-                                                                       e->err.p);
+        k_cleaf<<<blocks_for(na), 64 * kWavesPerBlock, 0, C.stream>>>(T, BVv, C.active, na, e->cfg.c, cnt, C.err);
         SPAI_HIP(hipGetLastError());
         if (timed) SPAI_TRY(stamp(0, false));
         if (kind == SPAI_EVAL_NET) {
             if (timed) SPAI_TRY(stamp(1, true));
-            SPAI_TRY(net_eval(e->net, e->stream, cnt, na, B.x.p, B.logits.p, B.value.p));
+            SPAI_TRY(net_eval(C.net, C.stream, cnt, na, B.x.p, B.logits.p, B.value.p));
             if (timed) SPAI_TRY(stamp(1, false));
         }
         if (timed) SPAI_TRY(stamp(2, true));
-        k_cexpand<<<blocks_for(na), 64 * kWavesPerBlock, 0, e->stream>>>(T, BVv, na, cnt, kind, e->err.p);
+        k_cexpand<<<blocks_for(na), 64 * kWavesPerBlock, 0, C.stream>>>(T, BVv, na, cnt, kind, C.err);
         SPAI_HIP(hipGetLastError());
         if (timed) SPAI_TRY(stamp(2, false));
     }
+    return SPAI_OK;
+}
+
+int chain_finish(spai_chess *e, const Chain &C, double *evals_out) {
+    if (evals_out) *evals_out = 0;
+    if (!C.n) return SPAI_OK;
+    const uint32_t na = C.n, sims = C.sims;
     std::vector<uint32_t> counts(sims);
-    SPAI_HIP(hipMemcpyAsync(counts.data(), B.counts.p, 4 * sims, hipMemcpyDeviceToHost, e->stream));
-    SPAI_TRY(check_err(e));
+    uint32_t f = 0;
+    SPAI_HIP(hipMemcpyAsync(counts.data(), C.batch->counts.p, 4 * sims, hipMemcpyDeviceToHost, C.stream));
+    SPAI_HIP(hipMemcpyAsync(&f, C.err, 4, hipMemcpyDeviceToHost, C.stream));
+    SPAI_HIP(hipStreamSynchronize(C.stream));
+    if (f) {
+        SPAI_HIP(hipMemsetAsync(C.err, 0, 4, C.stream));
+        return err_code(e, f);
+    }
     double ev = 0;
     for (uint32_t c : counts) ev += c;
     if (evals_out) *evals_out = ev;
     // per-kernel sampled times (event pairs in launch order)
-    if (tm.enabled) {
-        for (size_t k = 0; k + 1 < tm.used; k += 2) {
+    KernelTimer *tm = C.timer;
+    if (tm && tm->enabled) {
+        for (size_t k = 0; k + 1 < tm->used; k += 2) {
             float ms = 0;
-            SPAI_HIP(hipEventElapsedTime(&ms, tm.ev[k], tm.ev[k + 1]));
-            const int which = tm.which[k / 2];
-            tm.total_ms[which] += ms;
-            tm.launches[which] += 1;
+            SPAI_HIP(hipEventElapsedTime(&ms, tm->ev[k], tm->ev[k + 1]));
+            const int which = tm->which[k / 2];
+            tm->total_ms[which] += ms;
+            tm->launches[which] += 1;
         }
         // items: trees for select/expand, leaves for the forward (exact per iteration)
         for (uint32_t it = 0; it < sims; it += 8) {
-            tm.items[0] += na;
-            tm.items[1] += counts[it];
-            tm.items[2] += counts[it];
+            tm->items[0] += na;
+            tm->items[1] += counts[it];
+            tm->items[2] += counts[it];
         }
-        tm.used = 0;
-        tm.which.clear();
+        tm->used = 0;
+        tm->which.clear();
     }
-    (void)Tr;
     return SPAI_OK;
+}
+
+namespace {
+// the engine's own chain over e->active[0, na): self-play's and spai_chess_search's search
+int run_search(spai_chess *e, uint32_t na, uint32_t sims, double *evals_out) {
+    const Chain C = engine_chain(e, na, sims);
+    SPAI_TRY(chain_launch(e, C));
+    return chain_finish(e, C, evals_out);
 }
 
 int root_stats(spai_chess *e, uint32_t na) {
@@ -763,6 +748,20 @@ int trees_advance(spai_chess *e, uint32_t n, const uint32_t *tree_idx, const uin
     for (uint32_t i = 0; i < n; ++i) {
         if (status) status[i] = (uint8_t)(out[i] & 0xFF);
         if (reps) reps[i] = out[i] >> 8;
+    }
+    return SPAI_OK;
+}
+
+int tree_children(spai_chess *e, uint32_t tree, uint16_t *moves, uint32_t *visits, uint32_t *n) {
+    Trees &Tr = e->trees;
+    SPAI_CHECK(tree < Tr.n, SPAI_ERR_INVALID, "tree %u out of range (%u trees)", tree, Tr.n);
+    SPAI_HIP(hipMemcpyAsync(e->active.p, &tree, 4, hipMemcpyHostToDevice, e->stream));
+    SPAI_TRY(root_stats(e, 1));
+    const uint32_t nch = Tr.h_nch[0];
+    if (n) *n = nch;
+    for (uint32_t k = 0; k < (uint32_t)kMaxMoves; ++k) {
+        if (moves) moves[k] = k < nch ? Tr.h_moves[k] : 0;
+        if (visits) visits[k] = k < nch ? Tr.h_visits[k] : 0;
     }
     return SPAI_OK;
 }

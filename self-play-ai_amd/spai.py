@@ -54,6 +54,8 @@ SYMBOLS = [
     "spai_chess_net_set_params", "spai_chess_learner_create", "spai_chess_learner_destroy",
     "spai_chess_learner_train_batch", "spai_chess_learner_train", "spai_chess_learner_params",
     "spai_chess_learner_grads", "spai_chess_learner_activation", "spai_chess_learner_last_batch",
+    "spai_chess_match_config_default", "spai_chess_match_run", "spai_chess_tree_children",
+    "spai_chess_match_set_one_stream",
     # tictactoe (spai_ttt.py)
     "spai_ttt_create", "spai_ttt_destroy", "spai_ttt_games_resize", "spai_ttt_games_write", "spai_ttt_games_read",
     "spai_ttt_legal_mask", "spai_ttt_apply", "spai_ttt_encode", "spai_ttt_mask_invalid", "spai_ttt_net_num_params",

@@ -6,6 +6,7 @@ Mirrors the reference's chess surface (joshua16266261/self-play-ai):
   Net (model/chess.rs)             -> ChessNet.forward
   Tree + Mcts::search (mcts.rs)    -> ChessEngine.trees_create / search / use_subtree
   SelfPlayWorker::self_play        -> ChessEngine.self_play
+  play() (main.rs:54-135)          -> ChessEngine.match
   Model::train (model/mod.rs)      -> ChessLearner.train_batch / train
   Learner::learn (learner.rs)      -> learn
 Every call goes through the HIP library; there is no CPU fallback.
@@ -26,6 +27,26 @@ assert STATE_DTYPE.itemsize == 80
 
 SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                    C.POINTER(C.c_float), C.POINTER(C.c_uint16))
+
+
+class ChessMatchPlayer(C.Structure):
+    _fields_ = [("eval", C.c_int32), ("num_searches", C.c_uint32), ("net", C.c_void_p)]
+
+
+class ChessMatchConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("opening_plies", C.c_uint32), ("max_plies", C.c_uint32),
+                ("moves_stride", C.c_uint32), ("seed", C.c_uint64), ("start", C.c_void_p)]
+
+
+class ChessMatchGame(C.Structure):
+    _fields_ = [("game_id", C.c_uint64), ("a_moves_first", C.c_int8), ("result_a", C.c_int8),
+                ("status", C.c_uint8), ("adjudicated", C.c_uint8), ("n_moves", C.c_uint32)]
+
+
+class ChessMatchStats(C.Structure):
+    _fields_ = [(k, C.c_double * 2) for k in ("a_wins", "draws", "b_wins", "sims", "evals")] + \
+               [(k, C.c_double) for k in ("adjudicated", "plies", "seconds")]
+
 
 _ready = False
 
@@ -69,6 +90,11 @@ def lib():
         L.spai_chess_set_timing.argtypes = [vp, i32]
         L.spai_chess_timing.argtypes = [vp, vp, vp, vp]
         L.spai_chess_net_set_params.argtypes = [vp, vp, C.c_size_t]
+        L.spai_chess_match_config_default.argtypes = [P(ChessMatchConfig)]
+        L.spai_chess_match_run.argtypes = [vp, P(ChessMatchPlayer), P(ChessMatchPlayer), u32, u64,
+                                           P(ChessMatchConfig), P(ChessMatchGame), vp, P(ChessMatchStats)]
+        L.spai_chess_tree_children.argtypes = [vp, u32, vp, vp, P(u32)]
+        L.spai_chess_match_set_one_stream.argtypes = [vp, i32]
         L.spai_chess_learner_create.argtypes = [vp, i32, vp, C.c_size_t, P(spai.AdamConfig), P(vp)]
         L.spai_chess_learner_destroy.argtypes = [vp]
         L.spai_chess_learner_train_batch.argtypes = [vp, u32, vp, vp, vp, vp]
@@ -256,6 +282,62 @@ class ChessEngine:
         w = C.c_float()
         _check(lib().spai_chess_tree_root(self.h, tree, _p(st), C.byref(n), C.byref(w)))
         return st[0], n.value, w.value
+
+    def tree_children(self, tree):
+        """root children of a tree without searching it: (moves uint16 [n], visits uint32 [n]);
+        n = 0 while the root is not expanded"""
+        mv = np.zeros(MAX_MOVES, np.uint16)
+        vis = np.zeros(MAX_MOVES, np.uint32)
+        n = C.c_uint32()
+        _check(lib().spai_chess_tree_children(self.h, tree, _p(mv), _p(vis), C.byref(n)))
+        return mv[:n.value].copy(), vis[:n.value].copy()
+
+    def match(self, a, b, n_games, game_id_base=0, opening_plies=2, max_plies=512, seed=0, start=None,
+              keep_moves=True):
+        """play() (main.rs:54-135) between two players over n_games chess games
+        (spai_chess_match_run).  A player is (eval_kind, ChessNet or None, num_searches).
+        Game i has id game_id_base + i; A plays the first searched ply of the even ids,
+        and both games of a pair (id // 2) share their start: start[pair - game_id_base
+        // 2] (a STATE_DTYPE array, opening_plies must be 0) or the start position plus
+        opening_plies drawn plies.  A game still Ongoing at max_plies plies (0: no limit)
+        is adjudicated a draw.  Returns (games, stats): per game a dict (game,
+        a_moves_first, result_a = +1 A won / 0 draw / -1 B won, status, adjudicated,
+        n_moves, moves np.uint16 or None), and the counts split by who moved first
+        ([0]: A), per-player sims and evals, adjudicated, plies, seconds."""
+        cfg = ChessMatchConfig()
+        _check(lib().spai_chess_match_config_default(C.byref(cfg)))
+        cfg.opening_plies, cfg.max_plies, cfg.seed = opening_plies, max_plies, seed
+        st_arr = None
+        if start is not None:
+            st_arr = np.ascontiguousarray(start, STATE_DTYPE)
+            n_pairs = (game_id_base + max(n_games, 1) - 1) // 2 - game_id_base // 2 + 1
+            if len(st_arr) < n_pairs:
+                raise ValueError(f"start holds {len(st_arr)} positions, the match has {n_pairs} pairs")
+            cfg.start = st_arr.ctypes.data
+        mv = None
+        if keep_moves:
+            # longest game: the ply limit, else the engine's history bound plus the opening
+            stride = max_plies if max_plies else self.cfg.max_moves + 4
+            stride = max(int(stride), int(opening_plies), 1)
+            cfg.moves_stride = stride
+            mv = np.zeros((max(n_games, 1), stride), np.uint16)
+        pl = [ChessMatchPlayer(int(kind), int(sims), net.h if net is not None else None) for kind, net, sims in (a, b)]
+        out = (ChessMatchGame * max(n_games, 1))()
+        st = ChessMatchStats()
+        _check(lib().spai_chess_match_run(self.h, C.byref(pl[0]), C.byref(pl[1]), n_games, game_id_base,
+                                          C.byref(cfg), out, _p(mv) if mv is not None else None, C.byref(st)))
+        games = [dict(game=int(g.game_id), a_moves_first=bool(g.a_moves_first), result_a=int(g.result_a),
+                      status=int(g.status), adjudicated=bool(g.adjudicated), n_moves=int(g.n_moves),
+                      moves=mv[i, :min(g.n_moves, mv.shape[1])].copy() if mv is not None else None)
+                 for i, g in enumerate(out[:n_games])]
+        stats = {k: [float(v) for v in getattr(st, k)] for k in ("a_wins", "draws", "b_wins", "sims", "evals")}
+        for k in ("adjudicated", "plies", "seconds"):
+            stats[k] = float(getattr(st, k))
+        return games, stats
+
+    def match_one_stream(self, on=True):
+        """measurement only: both chains of later matches on the engine's stream (default: two streams)"""
+        _check(lib().spai_chess_match_set_one_stream(self.h, 1 if on else 0))
 
     def self_play(self, n_games, game_id_base=0, keep=True, keep_policy=True, window=None):
         """SelfPlayWorker::self_play over n_games games; window: play them through
