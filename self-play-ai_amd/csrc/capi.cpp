@@ -82,25 +82,12 @@ void net_init_params(int game, int blocks, int hidden, uint64_t seed, float *par
 
 using namespace spai;
 
-#define ENG_CHECK(e)                                                           \
-    do {                                                                       \
-        if (!(e)) {                                                            \
-            set_error("null engine handle");                                   \
-            return SPAI_ERR_INVALID;                                           \
-        }                                                                      \
-        if (hipSetDevice((e)->device) != hipSuccess) {                         \
-            set_error("hipSetDevice(%d) failed", (e)->device);                 \
-            return SPAI_ERR_DEVICE;                                            \
-        }                                                                      \
+#define ENG_CHECK(e)                                                 \
+    do {                                                             \
+        SPAI_CHECK(e, SPAI_ERR_INVALID, "null engine handle");       \
+        SPAI_SET_DEVICE(e);                                          \
     } while (0)
 
-#define PTR_CHECK(p)                                                           \
-    do {                                                                       \
-        if (!(p)) {                                                            \
-            set_error("%s must not be NULL", #p);                              \
-            return SPAI_ERR_INVALID;                                           \
-        }                                                                      \
-    } while (0)
 
 extern "C" {
 
@@ -109,7 +96,7 @@ const char *spai_last_error(void) { return g_err; }
 const char *spai_version(void) { return "spai 0.3 (gfx950)"; }
 
 int spai_device_count(int *count) {
-    PTR_CHECK(count);
+    SPAI_PTR(count);
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
     *count = e == hipSuccess ? n : 0;
@@ -117,7 +104,7 @@ int spai_device_count(int *count) {
 }
 
 int spai_config_default(int game, spai_config *cfg) {
-    PTR_CHECK(cfg);
+    SPAI_PTR(cfg);
     SPAI_CHECK(game == SPAI_GAME_CONNECT4, SPAI_ERR_UNSUPPORTED, "device engine: only Connect4 is built (game %d)", game);
     *cfg = spai_config{};
     cfg->c = 2.0f;              // mcts.rs:49
@@ -131,8 +118,8 @@ int spai_config_default(int game, spai_config *cfg) {
 }
 
 int spai_engine_create(int game, const spai_config *cfg, int device, spai_engine **out) {
-    PTR_CHECK(cfg);
-    PTR_CHECK(out);
+    SPAI_PTR(cfg);
+    SPAI_PTR(out);
     SPAI_CHECK(game == SPAI_GAME_CONNECT4, SPAI_ERR_UNSUPPORTED, "device engine: only Connect4 is built (game %d)", game);
     SPAI_CHECK(cfg->eval <= SPAI_EVAL_HASH, SPAI_ERR_INVALID, "bad eval kind %u", cfg->eval);
     SPAI_CHECK(cfg->max_moves <= c4::kMaxPlies, SPAI_ERR_INVALID, "max_moves %u > 42", cfg->max_moves);
@@ -231,53 +218,53 @@ int spai_games_resize(spai_engine *e, uint32_t n) { ENG_CHECK(e); return rules_r
 int spai_games_reset(spai_engine *e, uint32_t first, uint32_t n) { ENG_CHECK(e); return rules_reset(e, first, n); }
 int spai_games_write(spai_engine *e, uint32_t first, uint32_t n, const spai_c4_state *s) {
     ENG_CHECK(e);
-    if (n) PTR_CHECK(s);
+    if (n) SPAI_PTR(s);
     return rules_write(e, first, n, s);
 }
 int spai_games_read(spai_engine *e, uint32_t first, uint32_t n, spai_c4_state *s) {
     ENG_CHECK(e);
-    if (n) PTR_CHECK(s);
+    if (n) SPAI_PTR(s);
     return rules_read(e, first, n, s);
 }
 int spai_legal_mask(spai_engine *e, uint32_t first, uint32_t n, uint32_t *mask) {
     ENG_CHECK(e);
-    if (n) PTR_CHECK(mask);
+    if (n) SPAI_PTR(mask);
     return rules_legal(e, first, n, mask);
 }
 int spai_apply(spai_engine *e, uint32_t first, uint32_t n, const int32_t *actions, int32_t *rc) {
     ENG_CHECK(e);
-    if (n) PTR_CHECK(actions);
+    if (n) SPAI_PTR(actions);
     return rules_apply(e, first, n, actions, rc);
 }
 int spai_value_terminated(spai_engine *e, uint32_t first, uint32_t n, float *v, uint8_t *t) {
     ENG_CHECK(e);
     if (n) {
-        PTR_CHECK(v);
-        PTR_CHECK(t);
+        SPAI_PTR(v);
+        SPAI_PTR(t);
     }
     return rules_value_term(e, first, n, v, t);
 }
 int spai_encode(spai_engine *e, uint32_t first, uint32_t n, float *out) {
     ENG_CHECK(e);
-    if (n) PTR_CHECK(out);
+    if (n) SPAI_PTR(out);
     return rules_encode(e, first, n, out);
 }
 int spai_mask_invalid(spai_engine *e, uint32_t first, uint32_t n, const float *p, uint32_t len, float *out) {
     ENG_CHECK(e);
     if (n) {
-        PTR_CHECK(p);
-        PTR_CHECK(out);
+        SPAI_PTR(p);
+        SPAI_PTR(out);
     }
     return rules_mask(e, first, n, p, len, out);
 }
 int spai_rules_bench(spai_engine *e, uint32_t n, uint32_t iters, double *ms) {
     ENG_CHECK(e);
-    PTR_CHECK(ms);
+    SPAI_PTR(ms);
     return rules_bench(e, n, iters, ms);
 }
 
 int spai_net_num_params(int game, int blocks, int hidden, size_t *count) {
-    PTR_CHECK(count);
+    SPAI_PTR(count);
     SPAI_CHECK(game == SPAI_GAME_CONNECT4 && blocks >= 0 && hidden > 0, SPAI_ERR_UNSUPPORTED,
                "net shape not supported (game %d, blocks %d, hidden %d)", game, blocks, hidden);
     *count = net_num_params(game, blocks, hidden);
@@ -285,7 +272,7 @@ int spai_net_num_params(int game, int blocks, int hidden, size_t *count) {
 }
 
 int spai_net_init_params(int game, int blocks, int hidden, uint64_t seed, float *params) {
-    PTR_CHECK(params);
+    SPAI_PTR(params);
     SPAI_CHECK(game == SPAI_GAME_CONNECT4 && blocks >= 0 && hidden > 0, SPAI_ERR_UNSUPPORTED,
                "net shape not supported");
     net_init_params(game, blocks, hidden, seed, params);
@@ -295,7 +282,7 @@ int spai_net_init_params(int game, int blocks, int hidden, uint64_t seed, float 
 int spai_net_create(spai_engine *e, int blocks, int hidden, const float *params, size_t nparams, int dtype,
                     spai_net **out) {
     ENG_CHECK(e);
-    PTR_CHECK(out);
+    SPAI_PTR(out);
     return net_create(e, blocks, hidden, params, nparams, dtype, out);
 }
 
@@ -311,23 +298,23 @@ int spai_net_destroy(spai_net *n) {
 }
 
 int spai_net_forward(spai_net *n, uint32_t cnt, const float *x, float *logits, float *value) {
-    PTR_CHECK(n);
+    SPAI_PTR(n);
     ENG_CHECK(n->eng);
     if (cnt) {
-        PTR_CHECK(x);
-        PTR_CHECK(logits);
-        PTR_CHECK(value);
+        SPAI_PTR(x);
+        SPAI_PTR(logits);
+        SPAI_PTR(value);
     }
     return net_forward_x(n, cnt, x, logits, value);
 }
 
 int spai_predict(spai_net *n, uint32_t cnt, const spai_c4_state *s, float *priors, float *values) {
-    PTR_CHECK(n);
+    SPAI_PTR(n);
     ENG_CHECK(n->eng);
     if (cnt) {
-        PTR_CHECK(s);
-        PTR_CHECK(priors);
-        PTR_CHECK(values);
+        SPAI_PTR(s);
+        SPAI_PTR(priors);
+        SPAI_PTR(values);
     }
     return net_predict(n, cnt, s, priors, values);
 }
@@ -346,7 +333,7 @@ int spai_eval_cache_set_capacity(spai_engine *e, uint64_t entries) {
 
 int spai_eval_cache_get_stats(spai_engine *e, spai_eval_cache_stats *out) {
     ENG_CHECK(e);
-    PTR_CHECK(out);
+    SPAI_PTR(out);
     return eval_cache_stats(e, out);
 }
 
@@ -355,7 +342,7 @@ int spai_tree_reset(spai_engine *e, uint32_t t, const spai_c4_state *root) { ENG
 int spai_search(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, float *policy,
                 uint32_t *child_ids, float *child_visits, uint32_t *n_children) {
     ENG_CHECK(e);
-    if (n) PTR_CHECK(tree_idx);
+    if (n) SPAI_PTR(tree_idx);
     return search(e, n, tree_idx, num_searches, policy, child_ids, child_visits, n_children, nullptr);
 }
 int spai_tree_use_subtree(spai_engine *e, uint32_t t, uint32_t child) { ENG_CHECK(e); return tree_use_subtree(e, t, child); }
@@ -365,7 +352,7 @@ int spai_tree_node(spai_engine *e, uint32_t t, uint32_t node, spai_c4_state *st,
 }
 int spai_tree_size(spai_engine *e, uint32_t t, uint32_t *nodes) {
     ENG_CHECK(e);
-    PTR_CHECK(nodes);
+    SPAI_PTR(nodes);
     return tree_size(e, t, nodes);
 }
 
@@ -392,7 +379,7 @@ int spai_selfplay_stream(spai_engine *e, uint32_t n_games, uint32_t window, uint
 }
 
 int spai_match_config_default(spai_match_config *cfg) {
-    PTR_CHECK(cfg);
+    SPAI_PTR(cfg);
     *cfg = spai_match_config{};
     cfg->struct_size = (uint32_t)sizeof(spai_match_config);
     cfg->opening_plies = 4;
@@ -403,9 +390,9 @@ int spai_match_config_default(spai_match_config *cfg) {
 int spai_match_run(spai_engine *e, const spai_match_player *a, const spai_match_player *b, uint32_t n_games,
                    uint64_t gid_base, const spai_match_config *cfg, spai_match_game *games, spai_match_stats *stats) {
     ENG_CHECK(e);
-    PTR_CHECK(a);
-    PTR_CHECK(b);
-    PTR_CHECK(cfg);
+    SPAI_PTR(a);
+    SPAI_PTR(b);
+    SPAI_PTR(cfg);
     SPAI_CHECK(cfg->struct_size == sizeof(spai_match_config), SPAI_ERR_INVALID,
                "spai_match_config.struct_size %u, expected %zu", cfg->struct_size, sizeof(spai_match_config));
     SPAI_CHECK(cfg->opening_plies <= 6, SPAI_ERR_INVALID, "opening_plies %u > 6", cfg->opening_plies);
@@ -444,22 +431,22 @@ int spai_engine_timing(spai_engine *e, double *avg_ms, double *launches) {
 }
 
 int spai_net_phase_cycles(spai_net *n, uint32_t count, double *cycles) {
-    PTR_CHECK(n);
-    PTR_CHECK(cycles);
+    SPAI_PTR(n);
+    SPAI_PTR(cycles);
     ENG_CHECK(n->eng);
     return net_phase_stamps(n, count, cycles);
 }
 
 int spai_net_bench(spai_net *n, uint32_t count, uint32_t iters, double *ms) {
-    PTR_CHECK(n);
-    PTR_CHECK(ms);
+    SPAI_PTR(n);
+    SPAI_PTR(ms);
     ENG_CHECK(n->eng);
     return net_bench(n, count, iters, ms);
 }
 
 int spai_net_bench_conc(spai_net *n, uint32_t count, uint32_t iters, int conc, double *ms) {
-    PTR_CHECK(n);
-    PTR_CHECK(ms);
+    SPAI_PTR(n);
+    SPAI_PTR(ms);
     ENG_CHECK(n->eng);
     if (conc < 1) {
         set_error("conc %d < 1", conc);
@@ -481,7 +468,7 @@ int spai_engine_timing_items(spai_engine *e, double *total_ms, double *items) {
 
 // ---------------------------------------------------------------- learner
 int spai_adam_config_default(spai_adam_config *cfg) {
-    PTR_CHECK(cfg);
+    SPAI_PTR(cfg);
     cfg->lr = 1e-3f;   // Adam::default().build(vs, 1e-3) (model/mod.rs:107)
     cfg->beta1 = 0.9f;
     cfg->beta2 = 0.999f;
@@ -494,8 +481,8 @@ int spai_adam_config_default(spai_adam_config *cfg) {
 int spai_learner_create(spai_engine *e, int blocks, int hidden, const float *params, size_t n,
                         const spai_adam_config *cfg, spai_learner **out) {
     ENG_CHECK(e);
-    PTR_CHECK(params);
-    PTR_CHECK(out);
+    SPAI_PTR(params);
+    SPAI_PTR(out);
     return learner_create(e, blocks, hidden, params, n, cfg, out);
 }
 
@@ -507,92 +494,92 @@ int spai_learner_destroy(spai_learner *l) {
 
 int spai_learner_train_batch(spai_learner *l, uint32_t n, const float *states, const float *policies,
                              const float *values, float *loss) {
-    PTR_CHECK(l);
-    PTR_CHECK(states);
-    PTR_CHECK(policies);
-    PTR_CHECK(values);
+    SPAI_PTR(l);
+    SPAI_PTR(states);
+    SPAI_PTR(policies);
+    SPAI_PTR(values);
     ENG_CHECK(l->eng);
     return learner_train_batch(l, n, states, policies, values, loss);
 }
 
 int spai_learner_train_batches(spai_learner *l, uint32_t k, uint32_t n, const float *states, const float *policies,
                                const float *values, float *losses) {
-    PTR_CHECK(l);
-    PTR_CHECK(states);
-    PTR_CHECK(policies);
-    PTR_CHECK(values);
+    SPAI_PTR(l);
+    SPAI_PTR(states);
+    SPAI_PTR(policies);
+    SPAI_PTR(values);
     ENG_CHECK(l->eng);
     return learner_train_batches(l, k, n, states, policies, values, losses);
 }
 
 int spai_learner_params(spai_learner *l, float *params, size_t n) {
-    PTR_CHECK(l);
-    PTR_CHECK(params);
+    SPAI_PTR(l);
+    SPAI_PTR(params);
     ENG_CHECK(l->eng);
     return learner_params(l, params, n, false);
 }
 
 int spai_learner_grads(spai_learner *l, float *grads, size_t n) {
-    PTR_CHECK(l);
-    PTR_CHECK(grads);
+    SPAI_PTR(l);
+    SPAI_PTR(grads);
     ENG_CHECK(l->eng);
     return learner_params(l, grads, n, true);
 }
 
 int spai_learner_activation(spai_learner *l, int layer, float *out, size_t n) {
-    PTR_CHECK(l);
-    PTR_CHECK(out);
+    SPAI_PTR(l);
+    SPAI_PTR(out);
     ENG_CHECK(l->eng);
     return learner_activation(l, layer, out, n);
 }
 
 int spai_comm_unique_id(uint8_t *id) {
-    PTR_CHECK(id);
+    SPAI_PTR(id);
     return comm_unique_id(id);
 }
 
 int spai_learner_set_comm(spai_learner *l, int rank, int world, const uint8_t *id) {
-    PTR_CHECK(l);
+    SPAI_PTR(l);
     ENG_CHECK(l->eng);
-    if (world > 1) PTR_CHECK(id);   // world 1: an id makes a 1-rank RCCL communicator, NULL none
+    if (world > 1) SPAI_PTR(id);   // world 1: an id makes a 1-rank RCCL communicator, NULL none
     return learner_set_comm(l, rank, world, id);
 }
 
 int spai_learner_broadcast(spai_learner *l, int root) {
-    PTR_CHECK(l);
+    SPAI_PTR(l);
     ENG_CHECK(l->eng);
     return learner_broadcast(l, root);
 }
 
 int spai_learner_set_host_comm(spai_learner *l, int rank, int world, spai_host_allreduce fn, void *user) {
-    PTR_CHECK(l);
+    SPAI_PTR(l);
     ENG_CHECK(l->eng);
     return learner_set_host_comm(l, rank, world, fn, user);
 }
 
 int spai_learner_last_batch(spai_learner *l, uint32_t *n) {
-    PTR_CHECK(l);
-    PTR_CHECK(n);
+    SPAI_PTR(l);
+    SPAI_PTR(n);
     *n = l->last_batch;
     return SPAI_OK;
 }
 
 // ---------------------------------------------------------------- checkpoints
 int spai_params_save_safetensors(int game, int blocks, int hidden, const float *params, size_t n, const char *path) {
-    PTR_CHECK(params);
-    PTR_CHECK(path);
+    SPAI_PTR(params);
+    SPAI_PTR(path);
     return params_save_safetensors(game, blocks, hidden, params, n, path);
 }
 
 int spai_params_load_safetensors(int game, int blocks, int hidden, const char *path, float *params, size_t n) {
-    PTR_CHECK(params);
-    PTR_CHECK(path);
+    SPAI_PTR(params);
+    SPAI_PTR(path);
     return params_load_safetensors(game, blocks, hidden, path, params, n);
 }
 
 // ---------------------------------------------------------------- replay + pipeline
 int spai_replay_create(uint32_t capacity, spai_replay **out) {
-    PTR_CHECK(out);
+    SPAI_PTR(out);
     return replay_create(capacity, out);
 }
 
@@ -602,33 +589,33 @@ int spai_replay_destroy(spai_replay *r) {
 }
 
 int spai_replay_push(spai_replay *r, uint32_t n, const float *states, const float *policies, const float *values) {
-    PTR_CHECK(r);
+    SPAI_PTR(r);
     if (n) {
-        PTR_CHECK(states);
-        PTR_CHECK(policies);
-        PTR_CHECK(values);
+        SPAI_PTR(states);
+        SPAI_PTR(policies);
+        SPAI_PTR(values);
     }
     return replay_push(r, n, states, policies, values);
 }
 
 int spai_replay_pop(spai_replay *r, uint32_t n, float *states, float *policies, float *values) {
-    PTR_CHECK(r);
+    SPAI_PTR(r);
     if (n) {
-        PTR_CHECK(states);
-        PTR_CHECK(policies);
-        PTR_CHECK(values);
+        SPAI_PTR(states);
+        SPAI_PTR(policies);
+        SPAI_PTR(values);
     }
     return replay_pop_now(r, n, states, policies, values);
 }
 
 int spai_replay_size(spai_replay *r, uint32_t *n) {
-    PTR_CHECK(r);
-    PTR_CHECK(n);
+    SPAI_PTR(r);
+    SPAI_PTR(n);
     return replay_size(r, n);
 }
 
 int spai_choose_multiple(uint32_t n, uint32_t k, uint64_t seed, uint64_t stream, uint32_t *out) {
-    PTR_CHECK(out);
+    SPAI_PTR(out);
     std::vector<uint32_t> v;
     choose_multiple(n, k, seed, stream, v);
     std::copy(v.begin(), v.end(), out);
@@ -642,7 +629,7 @@ int spai_choose_multiple(uint32_t n, uint32_t k, uint64_t seed, uint64_t stream,
                (unsigned)(cfg)->struct_size, sizeof(spai_pipeline_config))
 
 int spai_pipeline_config_default(spai_pipeline_config *cfg) {
-    PTR_CHECK(cfg);
+    SPAI_PTR(cfg);
     PIPE_CFG_CHECK(cfg);
     static const int dev0 = 0;
     *cfg = spai_pipeline_config{};
@@ -667,18 +654,18 @@ int spai_pipeline_config_default(spai_pipeline_config *cfg) {
 
 int spai_pipeline_run(const spai_pipeline_config *cfg, const float *init_params, size_t n_params,
                       spai_pipeline_stats *stats) {
-    PTR_CHECK(cfg);
+    SPAI_PTR(cfg);
     PIPE_CFG_CHECK(cfg);
-    PTR_CHECK(init_params);
+    SPAI_PTR(init_params);
     return pipeline_run(cfg, init_params, n_params, stats);
 }
 
 int spai_learner_train(spai_learner *l, uint32_t n, const float *states, const float *policies, const float *values,
                        uint32_t epochs, uint32_t batch, uint64_t seed, float *loss) {
-    PTR_CHECK(l);
-    PTR_CHECK(states);
-    PTR_CHECK(policies);
-    PTR_CHECK(values);
+    SPAI_PTR(l);
+    SPAI_PTR(states);
+    SPAI_PTR(policies);
+    SPAI_PTR(values);
     ENG_CHECK(l->eng);
     return learner_train_epochs(l, n, states, policies, values, epochs, batch, seed, loss);
 }

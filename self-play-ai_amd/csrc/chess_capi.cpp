@@ -7,25 +7,12 @@
 using namespace spai;
 using namespace spai::chess;
 
-#define CH_CHECK(e)                                                            \
-    do {                                                                       \
-        if (!(e)) {                                                            \
-            set_error("null chess engine handle");                             \
-            return SPAI_ERR_INVALID;                                           \
-        }                                                                      \
-        if (hipSetDevice((e)->device) != hipSuccess) {                         \
-            set_error("hipSetDevice(%d) failed", (e)->device);                 \
-            return SPAI_ERR_DEVICE;                                            \
-        }                                                                      \
+#define CH_CHECK(e)                                                       \
+    do {                                                                  \
+        SPAI_CHECK(e, SPAI_ERR_INVALID, "null chess engine handle");      \
+        SPAI_SET_DEVICE(e);                                               \
     } while (0)
 
-#define CH_PTR(p)                                                              \
-    do {                                                                       \
-        if (!(p)) {                                                            \
-            set_error("%s must not be NULL", #p);                              \
-            return SPAI_ERR_INVALID;                                           \
-        }                                                                      \
-    } while (0)
 
 namespace {
 void release_all(spai_chess *e) {
@@ -79,7 +66,7 @@ void release_all(spai_chess *e) {
 extern "C" {
 
 int spai_chess_config_default(spai_config *cfg) {
-    CH_PTR(cfg);
+    SPAI_PTR(cfg);
     *cfg = spai_config{};
     cfg->c = 2.0f;              // mcts.rs:49
     cfg->num_searches = 400;    // BASELINE config 4 (chess, 400 sims/move)
@@ -100,8 +87,8 @@ int spai_chess_config_default(spai_config *cfg) {
 }
 
 int spai_chess_create(const spai_config *cfg, int device, spai_chess **out) {
-    CH_PTR(cfg);
-    CH_PTR(out);
+    SPAI_PTR(cfg);
+    SPAI_PTR(out);
     SPAI_CHECK(cfg->eval <= SPAI_EVAL_HASH, SPAI_ERR_INVALID, "bad eval kind %u", cfg->eval);
     SPAI_CHECK(cfg->max_moves >= 1 && cfg->max_trees >= 1 && cfg->num_searches >= 1, SPAI_ERR_INVALID,
                "max_moves, max_trees and num_searches must be >= 1");
@@ -149,13 +136,13 @@ int spai_chess_games_resize(spai_chess *e, uint32_t n) {
 
 int spai_chess_games_write(spai_chess *e, uint32_t first, uint32_t n, const spai_chess_state *s) {
     CH_CHECK(e);
-    if (n) CH_PTR(s);
+    if (n) SPAI_PTR(s);
     return slots_write(e, first, n, s);
 }
 
 int spai_chess_games_read(spai_chess *e, uint32_t first, uint32_t n, spai_chess_state *s) {
     CH_CHECK(e);
-    if (n) CH_PTR(s);
+    if (n) SPAI_PTR(s);
     return slots_read(e, first, n, s);
 }
 
@@ -166,7 +153,7 @@ int spai_chess_legal_moves(spai_chess *e, uint32_t first, uint32_t n, uint16_t *
 
 int spai_chess_apply(spai_chess *e, uint32_t first, uint32_t n, const uint16_t *moves, int32_t *rc) {
     CH_CHECK(e);
-    if (n) CH_PTR(moves);
+    if (n) SPAI_PTR(moves);
     return slots_apply(e, first, n, moves, rc);
 }
 
@@ -178,19 +165,19 @@ int spai_chess_status(spai_chess *e, uint32_t first, uint32_t n, uint8_t *status
 
 int spai_chess_rules_bench(spai_chess *e, uint32_t first, uint32_t n, uint32_t iters, double *ms) {
     CH_CHECK(e);
-    CH_PTR(ms);
+    SPAI_PTR(ms);
     return slots_rules_bench(e, first, n, iters, ms);
 }
 
 int spai_chess_perft(spai_chess *e, uint32_t slot, int depth, uint64_t *counts) {
     CH_CHECK(e);
-    CH_PTR(counts);
+    SPAI_PTR(counts);
     return perft(e, slot, depth, counts);
 }
 
 int spai_chess_encode(spai_chess *e, uint32_t first, uint32_t n, float *out) {
     CH_CHECK(e);
-    if (n) CH_PTR(out);
+    if (n) SPAI_PTR(out);
     return slots_encode(e, first, n, out);
 }
 
@@ -198,14 +185,14 @@ int spai_chess_mask_invalid(spai_chess *e, uint32_t first, uint32_t n, const flo
                             float *out) {
     CH_CHECK(e);
     if (n) {
-        CH_PTR(policy);
-        CH_PTR(out);
+        SPAI_PTR(policy);
+        SPAI_PTR(out);
     }
     return slots_mask(e, first, n, policy, len, out);
 }
 
 int spai_chess_move_index(int side, uint16_t move, int32_t *index) {
-    CH_PTR(index);
+    SPAI_PTR(index);
     SPAI_CHECK(side == 0 || side == 1, SPAI_ERR_INVALID, "side must be 0 or 1");
     SPAI_CHECK(((move >> 12) & 7) <= 4 && (move & 63) != ((move >> 6) & 63), SPAI_ERR_INVALID, "bad move code %u",
                move);
@@ -214,7 +201,7 @@ int spai_chess_move_index(int side, uint16_t move, int32_t *index) {
 }
 
 int spai_chess_index_move(int side, int32_t index, uint16_t *move) {
-    CH_PTR(move);
+    SPAI_PTR(move);
     SPAI_CHECK(side == 0 || side == 1, SPAI_ERR_INVALID, "side must be 0 or 1");
     SPAI_CHECK(index >= 0 && index < kPolicy, SPAI_ERR_INVALID, "index %d out of [0, 4672)", index);
     *move = (uint16_t)get_action_host(side, index);
@@ -222,14 +209,14 @@ int spai_chess_index_move(int side, int32_t index, uint16_t *move) {
 }
 
 int spai_chess_net_num_params(int blocks, size_t *count) {
-    CH_PTR(count);
+    SPAI_PTR(count);
     SPAI_CHECK(blocks >= 0, SPAI_ERR_INVALID, "blocks < 0");
     *count = net_num_params(blocks);
     return SPAI_OK;
 }
 
 int spai_chess_net_init_params(int blocks, uint64_t seed, float *params) {
-    CH_PTR(params);
+    SPAI_PTR(params);
     SPAI_CHECK(blocks >= 0, SPAI_ERR_INVALID, "blocks < 0");
     net_init_params(blocks, seed, params);
     return SPAI_OK;
@@ -237,7 +224,7 @@ int spai_chess_net_init_params(int blocks, uint64_t seed, float *params) {
 
 int spai_chess_net_create(spai_chess *e, int blocks, const float *params, size_t n_params, spai_chess_net **out) {
     CH_CHECK(e);
-    CH_PTR(out);
+    SPAI_PTR(out);
     return net_create(e, blocks, params, n_params, out);
 }
 
@@ -250,22 +237,22 @@ int spai_chess_net_destroy(spai_chess_net *net) {
 }
 
 int spai_chess_net_forward(spai_chess_net *net, uint32_t n, const float *x, float *logits, float *value) {
-    CH_PTR(net);
+    SPAI_PTR(net);
     CH_CHECK(net->eng);
     if (n) {
-        CH_PTR(x);
-        CH_PTR(logits);
-        CH_PTR(value);
+        SPAI_PTR(x);
+        SPAI_PTR(logits);
+        SPAI_PTR(value);
     }
     return net_forward_host(net, n, x, logits, value);
 }
 
 int spai_chess_predict(spai_chess_net *net, uint32_t first, uint32_t n, float *priors, float *values) {
-    CH_PTR(net);
+    SPAI_PTR(net);
     CH_CHECK(net->eng);
     if (n) {
-        CH_PTR(priors);
-        CH_PTR(values);
+        SPAI_PTR(priors);
+        SPAI_PTR(values);
     }
     return net_predict(net, first, n, priors, values);
 }
@@ -285,7 +272,7 @@ int spai_chess_trees_create(spai_chess *e, uint32_t n) {
 int spai_chess_search(spai_chess *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, float *policy,
                       uint32_t *child_ids, float *child_visits, uint16_t *child_moves, uint32_t *n_children) {
     CH_CHECK(e);
-    CH_PTR(tree_idx);
+    SPAI_PTR(tree_idx);
     return search(e, n, tree_idx, num_searches, policy, child_ids, child_visits, child_moves, n_children, nullptr);
 }
 
@@ -307,8 +294,8 @@ int spai_chess_tree_root(spai_chess *e, uint32_t tree, spai_chess_state *root, u
 int spai_chess_trees_advance(spai_chess *e, uint32_t n, const uint32_t *tree_idx, const uint32_t *child_index,
                              uint8_t *status, uint32_t *reps) {
     CH_CHECK(e);
-    CH_PTR(tree_idx);
-    CH_PTR(child_index);
+    SPAI_PTR(tree_idx);
+    SPAI_PTR(child_index);
     return trees_advance(e, n, tree_idx, child_index, status, reps);
 }
 
@@ -339,7 +326,7 @@ int spai_chess_match_set_one_stream(spai_chess *e, int on) {
 }
 
 int spai_chess_match_config_default(spai_chess_match_config *cfg) {
-    CH_PTR(cfg);
+    SPAI_PTR(cfg);
     *cfg = spai_chess_match_config{};
     cfg->struct_size = (uint32_t)sizeof(spai_chess_match_config);
     cfg->opening_plies = 2;
@@ -351,9 +338,9 @@ int spai_chess_match_run(spai_chess *e, const spai_chess_match_player *a, const 
                          uint32_t n_games, uint64_t gid_base, const spai_chess_match_config *cfg,
                          spai_chess_match_game *games, uint16_t *moves, spai_chess_match_stats *stats) {
     CH_CHECK(e);
-    CH_PTR(a);
-    CH_PTR(b);
-    CH_PTR(cfg);
+    SPAI_PTR(a);
+    SPAI_PTR(b);
+    SPAI_PTR(cfg);
     SPAI_CHECK(cfg->struct_size == sizeof(spai_chess_match_config), SPAI_ERR_INVALID,
                "spai_chess_match_config.struct_size %u, expected %zu", cfg->struct_size,
                sizeof(spai_chess_match_config));

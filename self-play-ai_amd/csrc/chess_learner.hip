@@ -44,23 +44,33 @@
 // channel, per-thread partials in a fixed element order and a fixed LDS tree;
 // linear gradients: one thread per entry, samples in order; loss: per-sample
 // terms, summed on the host in order.
+//
+// This file holds what is chess's: the conv, weight-gradient and head kernels, the
+// step's launch chain and the entry points.  The BatchNorm and Adam kernels
+// (k_lc_bn_fwd<64>, k_lc_bn_bwd<64>, k_lc_adam), the workgroup reductions, the
+// learner's state, the staged train step and Model::train's epoch loop are
+// learner_common.h's, shared with ttt_learner.hip.
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 #include <new>
 #include <vector>
 
 #include "chess_engine.h"
+#include "learner_common.h"
 
 namespace spai {
 namespace chess {
 namespace {
 
+using lc::block_max;
+using lc::block_sum;
+using lc::Conv;
+using lc::kBnThreads;
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kCells = 64, kHid = 256, kPolC = 73, kMaxBlocks = 40;
 constexpr int kEnc = kPlanes * kCells;   // 1216
-constexpr int kBnThreads = 256;
 constexpr int kWgSamples = 8;            // samples per weight-gradient chunk
 constexpr int kConvKC3 = 16, kConvKC1 = 64;   // input channels per chunk: 3x3, 1x1
 
@@ -254,109 +264,6 @@ __global__ void k_cl_wreduce(const float *__restrict__ part, int chunks, int CO,
     dw[i] = acc;
 }
 
-// the workgroup's sum in a fixed order (every thread gets it)
-__device__ __forceinline__ float block_sum(float v, float *sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int o = kBnThreads / 2; o > 0; o >>= 1) {
-        if (t < o) sh[t] = sh[t] + sh[t + o];
-        __syncthreads();
-    }
-    const float r = sh[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ float block_max(float v, float *sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int o = kBnThreads / 2; o > 0; o >>= 1) {
-        if (t < o) sh[t] = fmaxf(sh[t], sh[t + o]);
-        __syncthreads();
-    }
-    const float r = sh[0];
-    __syncthreads();
-    return r;
-}
-
-// train-mode BatchNorm of channel blockIdx.x over the 64 B values z[:, c, :]: batch
-// mean and biased variance, a = relu(gamma xhat + beta (+ res)), and the running
-// statistics (momentum, unbiased variance)
-__global__ __launch_bounds__(kBnThreads) void k_cl_bn_fwd(const float *__restrict__ z, int C, int B,
-                                                          const float *__restrict__ gamma,
-                                                          const float *__restrict__ beta, float *__restrict__ run_mu,
-                                                          float *__restrict__ run_var, const float *__restrict__ res,
-                                                          float *__restrict__ a, float *__restrict__ mean_out,
-                                                          float *__restrict__ invstd_out, float momentum, float eps) {
-    __shared__ float sh[kBnThreads];
-    const int c = blockIdx.x, t = threadIdx.x, nn = kCells * B;
-    float acc = 0.0f;
-    for (int i = t; i < nn; i += kBnThreads) acc += z[((size_t)(i >> 6) * C + c) * kCells + (i & 63)];
-    const float mean = block_sum(acc, sh) / (float)nn;
-    acc = 0.0f;
-    for (int i = t; i < nn; i += kBnThreads) {
-        const float d = z[((size_t)(i >> 6) * C + c) * kCells + (i & 63)] - mean;
-        acc += d * d;
-    }
-    const float var = block_sum(acc, sh) / (float)nn;
-    const float invstd = 1.0f / sqrtf(var + eps);
-    const float g = gamma[c], be = beta[c];
-    for (int i = t; i < nn; i += kBnThreads) {
-        const size_t idx = ((size_t)(i >> 6) * C + c) * kCells + (i & 63);
-        float yv = g * ((z[idx] - mean) * invstd) + be;
-        if (res) yv += res[idx];
-        a[idx] = fmaxf(yv, 0.0f);
-    }
-    if (t == 0) {
-        mean_out[c] = mean;
-        invstd_out[c] = invstd;
-        run_mu[c] = (1.0f - momentum) * run_mu[c] + momentum * mean;
-        run_var[c] = (1.0f - momentum) * run_var[c] + momentum * (var * ((float)nn / (float)(nn - 1)));
-    }
-}
-
-// backward of ReLU + BatchNorm for channel blockIdx.x: dy = da [a > 0];
-// dbeta = sum dy, dgamma = sum dy xhat, dz = gamma invstd / nn (nn dy - dbeta - xhat dgamma),
-// dbias = sum dz.  keep_dy: da becomes dy (the skip connection's gradient).
-__global__ __launch_bounds__(kBnThreads) void k_cl_bn_bwd(float *__restrict__ da, const float *__restrict__ a,
-                                                          const float *__restrict__ z, int C, int B,
-                                                          const float *__restrict__ mean,
-                                                          const float *__restrict__ invstd,
-                                                          const float *__restrict__ gamma, float *__restrict__ dz,
-                                                          float *__restrict__ g_gamma, float *__restrict__ g_beta,
-                                                          float *__restrict__ g_bias, int keep_dy) {
-    __shared__ float sh[kBnThreads];
-    const int c = blockIdx.x, t = threadIdx.x, nn = kCells * B;
-    const float mu = mean[c], is = invstd[c];
-    float sb = 0.0f, sg = 0.0f;
-    for (int i = t; i < nn; i += kBnThreads) {
-        const size_t idx = ((size_t)(i >> 6) * C + c) * kCells + (i & 63);
-        const float dy = a[idx] > 0.0f ? da[idx] : 0.0f;
-        sb += dy;
-        sg += dy * ((z[idx] - mu) * is);
-    }
-    sb = block_sum(sb, sh);
-    sg = block_sum(sg, sh);
-    const float k = gamma[c] * is / (float)nn;
-    float sz = 0.0f;
-    for (int i = t; i < nn; i += kBnThreads) {
-        const size_t idx = ((size_t)(i >> 6) * C + c) * kCells + (i & 63);
-        const float dy = a[idx] > 0.0f ? da[idx] : 0.0f;
-        const float v = k * ((float)nn * dy - sb - ((z[idx] - mu) * is) * sg);
-        dz[idx] = v;
-        if (keep_dy) da[idx] = dy;
-        sz += v;
-    }
-    sz = block_sum(sz, sh);
-    if (t == 0) {
-        g_gamma[c] = sg;
-        g_beta[c] = sb;
-        g_bias[c] = sz;
-    }
-}
-
 // a conv with bias and no BN, channel blockIdx.x: d becomes d [a > 0] (a: its ReLU
 // output, or NULL for none), g_bias[c] = its sum
 __global__ __launch_bounds__(kBnThreads) void k_cl_bias_grad(float *__restrict__ d, const float *__restrict__ a, int C,
@@ -505,47 +412,18 @@ __global__ void k_cl_lin_grad(const float *__restrict__ dh1, const float *__rest
     }
 }
 
-// Adam, torch semantics (as ttt_learner.hip's k_tl_adam).  The BN running statistics
-// have gradient 0, so their moments stay 0 and they do not move.
-__global__ void k_cl_adam(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
-                          float *__restrict__ v, size_t n, float lr, float b1, float b2, float eps, float bc1,
-                          float bc2_sqrt) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float gi = g[i];
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    p[i] -= (lr / bc1) * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-}
-
-struct Conv {
-    int ci, co;
-    size_t w, b, g, be, mu, var;   // offsets into the flat parameter vector
-};
-
 }  // namespace
 
-struct Learner {
-    spai_chess *eng = nullptr;
+struct Learner : lc::Core {   // batch_in: [x: B*1216 | pi: B*4672 | z: B]
     int blocks = 0;
-    spai_adam_config cfg{};
-    uint64_t step = 0;
-    uint32_t max_batch = 0, last_batch = 0;
-    size_t n_params = 0;
     std::vector<Conv> convs;   // stem, 2*blocks residual
     size_t p1_w = 0, p1_b = 0, p2_w = 0, p2_b = 0, v_w = 0, v_b = 0, l1_w = 0, l1_b = 0, l2_w = 0, l2_b = 0;
-    DevBuf<float> p, g, m, v;              // parameters, gradients, Adam moments (flat)
-    DevBuf<float> batch_in;                // [x: B*1216 | pi: B*4672 | z: B]
-    float *stage = nullptr;                // its pinned host copy, then the loss terms [B*2]
     std::vector<DevBuf<float>> z, a;       // per trunk conv: pre-BN output, post-ReLU activation [B][256][64]
     DevBuf<float> stat;                    // per trunk conv: batch mean [256] | inverse std [256]
     DevBuf<float> ap1, logits, dlogits;    // policy head: relu(conv1x1) [B][256][64], logits and their gradient [B][4672]
     DevBuf<float> vc, h1, dh1, dvc;        // value head: [B][64], [B][256] and their gradients
     DevBuf<float> g0, g1, dz;              // backward: two activation-gradient buffers and dz, [B][256][64]
     DevBuf<float> wpart;                   // weight-gradient partials [chunks][9][256][256]
-    DevBuf<float> dpre, terms;
 };
 
 }  // namespace chess
@@ -558,13 +436,9 @@ using namespace spai::chess;
 
 namespace {
 
-constexpr size_t kBatchRow = kEnc + kPolicy + 1;   // floats of one sample in batch_in
-
 int alloc_batch(spai_chess_learner *L, uint32_t B) {
     if (B <= L->max_batch) return SPAI_OK;
-    SPAI_HIP(hipStreamSynchronize(L->eng->stream));   // nothing in flight reads the old buffers
-    L->max_batch = 0;
-    L->last_batch = 0;
+    SPAI_TRY(lc::core_grow_batch(*L, B));
     const size_t act = (size_t)B * kHid * kCells;
     for (size_t l = 0; l < L->convs.size(); ++l) {
         SPAI_TRY(L->z[l].alloc(act));
@@ -578,12 +452,6 @@ int alloc_batch(spai_chess_learner *L, uint32_t B) {
     SPAI_TRY(L->h1.alloc((size_t)B * kHid));
     SPAI_TRY(L->dh1.alloc((size_t)B * kHid));
     SPAI_TRY(L->wpart.alloc((size_t)((B + kWgSamples - 1) / kWgSamples) * 9 * kHid * kHid));
-    SPAI_TRY(L->dpre.alloc(B));
-    SPAI_TRY(L->terms.alloc((size_t)B * 2));
-    SPAI_TRY(L->batch_in.alloc((size_t)B * kBatchRow));
-    if (L->stage) (void)hipHostFree(L->stage);
-    L->stage = nullptr;
-    SPAI_HIP(hipHostMalloc((void **)&L->stage, (size_t)B * (kBatchRow + 2) * sizeof(float), hipHostMallocDefault));
     L->max_batch = B;
     return SPAI_OK;
 }
@@ -617,8 +485,9 @@ void conv_fwd(spai_chess_learner *L, int l, const float *in, const float *res, i
     const Conv &c = L->convs[l];
     float *P = L->p.p, *stat = L->stat.p + (size_t)l * 2 * kHid;
     conv_launch(0, 9, in, c.ci, P + c.w, P + c.b, 0, nullptr, L->z[l].p, c.co, B, st);
-    k_cl_bn_fwd<<<c.co, kBnThreads, 0, st>>>(L->z[l].p, c.co, B, P + c.g, P + c.be, P + c.mu, P + c.var, res,
-                                             L->a[l].p, stat, stat + kHid, L->cfg.bn_momentum, L->cfg.bn_eps);
+    lc::k_lc_bn_fwd<kCells><<<c.co, kBnThreads, 0, st>>>(L->z[l].p, c.co, B, P + c.g, P + c.be, P + c.mu, P + c.var,
+                                                         res, L->a[l].p, stat, stat + kHid, L->cfg.bn_momentum,
+                                                         L->cfg.bn_eps);
 }
 
 // da: gradient of layer l's activation (becomes dy when keep_dy); in: the layer's input
@@ -627,15 +496,15 @@ void conv_bwd(spai_chess_learner *L, int l, float *da, int keep_dy, const float 
               int B, hipStream_t st) {
     const Conv &c = L->convs[l];
     float *P = L->p.p, *G = L->g.p, *stat = L->stat.p + (size_t)l * 2 * kHid;
-    k_cl_bn_bwd<<<c.co, kBnThreads, 0, st>>>(da, L->a[l].p, L->z[l].p, c.co, B, stat, stat + kHid, P + c.g, L->dz.p,
-                                             G + c.g, G + c.be, G + c.b, keep_dy);
+    lc::k_lc_bn_bwd<kCells><<<c.co, kBnThreads, 0, st>>>(da, L->a[l].p, L->z[l].p, c.co, B, stat, stat + kHid, P + c.g,
+                                                         L->dz.p, G + c.g, G + c.be, G + c.b, keep_dy);
     wgrad_launch(L, 9, L->dz.p, c.co, in, c.ci, G + c.w, B, st);
     if (dx) conv_launch(1, 9, L->dz.p, c.co, P + c.w, nullptr, 0, addend, dx, c.ci, B, st);
 }
 
 // one train step on the batch already in batch_in
 int enqueue_step(spai_chess_learner *L, int B) {
-    hipStream_t st = L->eng->stream;
+    hipStream_t st = L->stream;
     float *P = L->p.p, *G = L->g.p;
     const float *x = L->batch_in.p, *pi = x + (size_t)B * kEnc, *zt = pi + (size_t)B * kPolicy;
     const int nb = L->blocks;
@@ -669,12 +538,7 @@ int enqueue_step(spai_chess_learner *L, int B) {
         conv_bwd(L, 1 + 2 * k, oth, 0, L->a[2 * k].p, cur, cur, B, st);
     }
     conv_bwd(L, 0, cur, 0, x, nullptr, nullptr, B, st);
-    L->step += 1;
-    const double t = (double)L->step;
-    const float bc1 = (float)(1.0 - std::pow((double)L->cfg.beta1, t));
-    const float bc2 = (float)std::sqrt(1.0 - std::pow((double)L->cfg.beta2, t));
-    k_cl_adam<<<(unsigned)((L->n_params + 255) / 256), 256, 0, st>>>(P, G, L->m.p, L->v.p, L->n_params, L->cfg.lr,
-                                                                      L->cfg.beta1, L->cfg.beta2, L->cfg.eps, bc1, bc2);
+    lc::adam_step(*L);
     SPAI_HIP(hipGetLastError());
     L->last_batch = (uint32_t)B;
     return SPAI_OK;
@@ -684,119 +548,63 @@ int train_batch(spai_chess_learner *L, uint32_t B, const float *states, const fl
                 float *loss3) {
     SPAI_CHECK(B >= 1 && B <= (1u << 16), SPAI_ERR_INVALID, "train_batch: batch of %u samples", B);
     SPAI_TRY(alloc_batch(L, B));
-    hipStream_t st = L->eng->stream;
-    memcpy(L->stage, states, (size_t)B * kEnc * 4);
-    memcpy(L->stage + (size_t)B * kEnc, policies, (size_t)B * kPolicy * 4);
-    memcpy(L->stage + (size_t)B * (kEnc + kPolicy), values, (size_t)B * 4);
-    SPAI_HIP(hipMemcpyAsync(L->batch_in.p, L->stage, (size_t)B * kBatchRow * 4, hipMemcpyHostToDevice, st));
-    SPAI_TRY(enqueue_step(L, (int)B));
-    float *terms = L->stage + (size_t)B * kBatchRow;
-    SPAI_HIP(hipMemcpyAsync(terms, L->terms.p, (size_t)B * 2 * 4, hipMemcpyDeviceToHost, st));
-    SPAI_HIP(hipStreamSynchronize(st));
-    double lp = 0, lv = 0;   // the fixed-order host sums of the step's loss terms
-    for (uint32_t b = 0; b < B; ++b) {
-        lp += terms[2 * b];
-        lv += terms[2 * b + 1];
-    }
-    if (loss3) {
-        loss3[1] = (float)(lp / B);
-        loss3[2] = (float)(lv / B);
-        loss3[0] = loss3[1] + loss3[2];
-    }
-    SPAI_CHECK(std::isfinite(lp) && std::isfinite(lv), SPAI_ERR_NAN, "chess learner: non-finite loss at step %llu",
-               (unsigned long long)L->step);
+    bool finite = true;
+    SPAI_TRY(lc::train_batch(*L, B, states, policies, values, loss3, &finite,
+                             [&](int b) { return enqueue_step(L, b); }));
+    // intended: chess alone makes a non-finite loss an error (spai.h); TicTacToe and Connect4 return it as the loss
+    SPAI_CHECK(finite, SPAI_ERR_NAN, "chess learner: non-finite loss at step %llu", (unsigned long long)L->step);
     return SPAI_OK;
 }
 
 void learner_free(spai_chess_learner *L) {
     for (auto &d : L->z) d.release();
     for (auto &d : L->a) d.release();
-    for (auto *d : {&L->p, &L->g, &L->m, &L->v, &L->batch_in, &L->stat, &L->ap1, &L->logits, &L->dlogits, &L->vc,
-                    &L->h1, &L->dh1, &L->dvc, &L->g0, &L->g1, &L->dz, &L->wpart, &L->dpre, &L->terms})
+    for (auto *d : {&L->stat, &L->ap1, &L->logits, &L->dlogits, &L->vc, &L->h1, &L->dh1, &L->dvc, &L->g0, &L->g1,
+                    &L->dz, &L->wpart})
         d->release();
-    if (L->stage) (void)hipHostFree(L->stage);
+    lc::core_free(*L);
     delete L;
 }
 
 int learner_init(spai_chess_learner *L, const float *params) {
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        const size_t o = off;
-        off += n;
-        return o;
-    };
-    auto conv = [&](int ci, int co) {
-        Conv c{};
-        c.ci = ci;
-        c.co = co;
-        c.w = take((size_t)co * ci * 9);
-        c.b = take(co);
-        c.g = take(co);
-        c.be = take(co);
-        c.mu = take(co);
-        c.var = take(co);
-        L->convs.push_back(c);
-    };
-    conv(kPlanes, kHid);
-    for (int i = 0; i < 2 * L->blocks; ++i) conv(kHid, kHid);
-    L->p1_w = take((size_t)kHid * kHid);
-    L->p1_b = take(kHid);
-    L->p2_w = take((size_t)kPolC * kHid);
-    L->p2_b = take(kPolC);
-    L->v_w = take(kHid);
-    L->v_b = take(1);
-    L->l1_w = take((size_t)kHid * kCells);
-    L->l1_b = take(kHid);
-    L->l2_w = take(kHid);
-    L->l2_b = take(1);
-    SPAI_CHECK(off == L->n_params, SPAI_ERR_INVALID, "chess learner layout: %zu != %zu", off, L->n_params);
-    const size_t n = L->n_params, nl = L->convs.size();
+    lc::Layout lay;
+    L->convs.push_back(lay.conv3x3_bn(kPlanes, kHid));
+    for (int i = 0; i < 2 * L->blocks; ++i) L->convs.push_back(lay.conv3x3_bn(kHid, kHid));
+    L->p1_w = lay.take((size_t)kHid * kHid);
+    L->p1_b = lay.take(kHid);
+    L->p2_w = lay.take((size_t)kPolC * kHid);
+    L->p2_b = lay.take(kPolC);
+    L->v_w = lay.take(kHid);
+    L->v_b = lay.take(1);
+    L->l1_w = lay.take((size_t)kHid * kCells);
+    L->l1_b = lay.take(kHid);
+    L->l2_w = lay.take(kHid);
+    L->l2_b = lay.take(1);
+    SPAI_CHECK(lay.off == L->n_params, SPAI_ERR_INVALID, "chess learner layout: %zu != %zu", lay.off, L->n_params);
+    const size_t nl = L->convs.size();
     L->z.resize(nl);
     L->a.resize(nl);
-    hipStream_t st = L->eng->stream;
-    for (auto *d : {&L->p, &L->g, &L->m, &L->v}) SPAI_TRY(d->alloc(n));
     SPAI_TRY(L->stat.alloc(nl * 2 * kHid));
-    SPAI_HIP(hipMemcpyAsync(L->p.p, params, n * 4, hipMemcpyHostToDevice, st));
-    for (auto *d : {&L->g, &L->m, &L->v}) SPAI_HIP(hipMemsetAsync(d->p, 0, n * 4, st));
-    SPAI_HIP(hipStreamSynchronize(st));   // params is the caller's
-    return SPAI_OK;
+    return lc::core_init(*L, params);
 }
 
 }  // namespace
-
-#define CL_PTR(p)                                                     \
-    do {                                                              \
-        if (!(p)) {                                                   \
-            set_error("%s must not be NULL", #p);                     \
-            return SPAI_ERR_INVALID;                                  \
-        }                                                             \
-    } while (0)
-#define CL_DEVICE(e)                                                  \
-    do {                                                              \
-        if (hipSetDevice((e)->device) != hipSuccess) {                \
-            set_error("hipSetDevice(%d) failed", (e)->device);        \
-            return SPAI_ERR_DEVICE;                                   \
-        }                                                             \
-    } while (0)
 
 extern "C" {
 
 int spai_chess_learner_create(spai_chess *e, int blocks, const float *params, size_t n_params,
                               const spai_adam_config *cfg, spai_chess_learner **out) {
-    CL_PTR(e);
-    CL_PTR(params);
-    CL_PTR(out);
+    SPAI_PTR(e);
+    SPAI_PTR(params);
+    SPAI_PTR(out);
     SPAI_CHECK(blocks >= 0 && blocks <= kMaxBlocks, SPAI_ERR_UNSUPPORTED, "chess learner: 0..%d blocks", kMaxBlocks);
     SPAI_CHECK(n_params == net_num_params(blocks), SPAI_ERR_INVALID, "expected %zu params, got %zu",
                net_num_params(blocks), n_params);
-    CL_DEVICE(e);
+    SPAI_SET_DEVICE(e);
     spai_chess_learner *L = new (std::nothrow) spai_chess_learner();
     SPAI_CHECK(L, SPAI_ERR_INVALID, "out of host memory");
-    L->eng = e;
+    lc::core_setup(*L, e->device, e->stream, n_params, cfg, kEnc, kPolicy);
     L->blocks = blocks;
-    L->n_params = n_params;
-    if (cfg) L->cfg = *cfg;
-    else (void)spai_adam_config_default(&L->cfg);
     const int rc = learner_init(L, params);
     if (rc != SPAI_OK) {
         learner_free(L);
@@ -808,82 +616,54 @@ int spai_chess_learner_create(spai_chess *e, int blocks, const float *params, si
 
 int spai_chess_learner_destroy(spai_chess_learner *L) {
     if (!L) return SPAI_OK;
-    (void)hipSetDevice(L->eng->device);
-    (void)hipStreamSynchronize(L->eng->stream);
+    (void)hipSetDevice(L->device);
+    (void)hipStreamSynchronize(L->stream);
     learner_free(L);
     return SPAI_OK;
 }
 
 int spai_chess_learner_train_batch(spai_chess_learner *L, uint32_t n, const float *states, const float *policies,
                                    const float *values, float *loss) {
-    CL_PTR(L);
-    CL_PTR(states);
-    CL_PTR(policies);
-    CL_PTR(values);
-    CL_DEVICE(L->eng);
+    SPAI_PTR(L);
+    SPAI_PTR(states);
+    SPAI_PTR(policies);
+    SPAI_PTR(values);
+    SPAI_SET_DEVICE(L);
     return train_batch(L, n, states, policies, values, loss);
 }
 
-// Model::train (model/mod.rs:100-149): a fresh Adam (the reference builds the optimizer
-// inside train), one permutation of the n samples, then `epochs` passes of
-// ceil(n / batch) train steps over the permuted samples (the last batch may be short)
+// Model::train: lc::train_epochs over this learner's train step
 int spai_chess_learner_train(spai_chess_learner *L, uint32_t n, const float *states, const float *policies,
                              const float *values, uint32_t epochs, uint32_t batch, uint64_t seed, float *loss) {
-    CL_PTR(L);
-    CL_PTR(states);
-    CL_PTR(policies);
-    CL_PTR(values);
-    CL_DEVICE(L->eng);
-    SPAI_CHECK(n >= 1 && batch >= 1, SPAI_ERR_INVALID, "train: need samples and a batch size");
-    hipStream_t st = L->eng->stream;
-    SPAI_HIP(hipMemsetAsync(L->m.p, 0, L->n_params * 4, st));
-    SPAI_HIP(hipMemsetAsync(L->v.p, 0, L->n_params * 4, st));
-    L->step = 0;
-    std::vector<uint32_t> perm;
-    choose_multiple(n, n, seed, 0x7EA1Bull, perm);
-    batch = std::min(batch, n);
-    std::vector<float> s((size_t)batch * kEnc), p((size_t)batch * kPolicy), v(batch);
-    const uint32_t nb = (n + batch - 1) / batch;
-    for (uint32_t ep = 0; ep < epochs; ++ep)
-        for (uint32_t b = 0; b < nb; ++b) {
-            const uint32_t lo = b * batch, m = std::min(batch, n - lo);
-            for (uint32_t i = 0; i < m; ++i) {
-                const uint32_t j = perm[lo + i];
-                memcpy(&s[(size_t)i * kEnc], states + (size_t)j * kEnc, kEnc * 4);
-                memcpy(&p[(size_t)i * kPolicy], policies + (size_t)j * kPolicy, kPolicy * 4);
-                v[i] = values[j];
-            }
-            SPAI_TRY(train_batch(L, m, s.data(), p.data(), v.data(), loss));
-        }
-    return SPAI_OK;
-}
-
-static int read_flat(spai_chess_learner *L, const float *src, float *dst, size_t n) {
-    SPAI_CHECK(n == L->n_params, SPAI_ERR_INVALID, "expected %zu params, got %zu", L->n_params, n);
-    hipStream_t st = L->eng->stream;
-    SPAI_HIP(hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToHost, st));
-    SPAI_HIP(hipStreamSynchronize(st));
-    return SPAI_OK;
+    SPAI_PTR(L);
+    SPAI_PTR(states);
+    SPAI_PTR(policies);
+    SPAI_PTR(values);
+    SPAI_SET_DEVICE(L);
+    return lc::train_epochs(*L, L->stream, L->xw, L->pw, n, states, policies, values, epochs, batch, seed,
+                            [&](uint32_t m, const float *s, const float *p, const float *v) {
+                                return train_batch(L, m, s, p, v, loss);
+                            });
 }
 
 int spai_chess_learner_params(spai_chess_learner *L, float *params, size_t n_params) {
-    CL_PTR(L);
-    CL_PTR(params);
-    CL_DEVICE(L->eng);
-    return read_flat(L, L->p.p, params, n_params);
+    SPAI_PTR(L);
+    SPAI_PTR(params);
+    SPAI_SET_DEVICE(L);
+    return lc::read_flat(*L, L->p.p, params, n_params);
 }
 
 int spai_chess_learner_grads(spai_chess_learner *L, float *grads, size_t n_params) {
-    CL_PTR(L);
-    CL_PTR(grads);
-    CL_DEVICE(L->eng);
-    return read_flat(L, L->g.p, grads, n_params);
+    SPAI_PTR(L);
+    SPAI_PTR(grads);
+    SPAI_SET_DEVICE(L);
+    return lc::read_flat(*L, L->g.p, grads, n_params);
 }
 
 int spai_chess_learner_activation(spai_chess_learner *L, int layer, float *out, size_t n) {
-    CL_PTR(L);
-    CL_PTR(out);
-    CL_DEVICE(L->eng);
+    SPAI_PTR(L);
+    SPAI_PTR(out);
+    SPAI_SET_DEVICE(L);
     const int nt = (int)L->convs.size();   // trunk layers 0 .. 2 blocks
     SPAI_CHECK(layer >= 0 && layer < nt + 3, SPAI_ERR_INVALID, "layer %d of %d", layer, nt + 3);
     SPAI_CHECK(L->last_batch > 0, SPAI_ERR_INVALID, "no train step yet");
@@ -891,23 +671,22 @@ int spai_chess_learner_activation(spai_chess_learner *L, int layer, float *out, 
     const size_t per = layer <= nt ? (size_t)kHid * kCells : layer == nt + 1 ? (size_t)kCells : (size_t)kHid;
     const size_t want = (size_t)L->last_batch * per;
     SPAI_CHECK(n == want, SPAI_ERR_INVALID, "expected %zu activations, got %zu", want, n);
-    hipStream_t st = L->eng->stream;
-    SPAI_HIP(hipMemcpyAsync(out, src, n * 4, hipMemcpyDeviceToHost, st));
-    SPAI_HIP(hipStreamSynchronize(st));
+    SPAI_HIP(hipMemcpyAsync(out, src, n * 4, hipMemcpyDeviceToHost, L->stream));
+    SPAI_HIP(hipStreamSynchronize(L->stream));
     return SPAI_OK;
 }
 
 int spai_chess_learner_last_batch(spai_chess_learner *L, uint32_t *n) {
-    CL_PTR(L);
-    CL_PTR(n);
+    SPAI_PTR(L);
+    SPAI_PTR(n);
     *n = L->last_batch;
     return SPAI_OK;
 }
 
 int spai_chess_net_set_params(spai_chess_net *net, const float *params, size_t n_params) {
-    CL_PTR(net);
-    CL_PTR(params);
-    CL_DEVICE(net->eng);
+    SPAI_PTR(net);
+    SPAI_PTR(params);
+    SPAI_SET_DEVICE(net->eng);
     return net_set_params(net, params, n_params);
 }
 

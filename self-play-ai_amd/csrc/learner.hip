@@ -26,7 +26,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "spai_internal.h"
+#include "learner_common.h"
 
 namespace spai {
 namespace {
@@ -1791,18 +1791,6 @@ static int stage_and_enqueue(spai_learner *L, uint32_t B, const float *states, c
     return SPAI_OK;
 }
 
-// the fixed-order host sums of one step's loss terms
-static void sum_loss(const float *terms, uint32_t B, float *loss3) {
-    double lp = 0, lv = 0;
-    for (uint32_t b = 0; b < B; ++b) {
-        lp += terms[2 * b];
-        lv += terms[2 * b + 1];
-    }
-    loss3[1] = (float)(lp / B);
-    loss3[2] = (float)(lv / B);
-    loss3[0] = loss3[1] + loss3[2];
-}
-
 int learner_train_batch(spai_learner *L, uint32_t B, const float *states, const float *policies, const float *values,
                         float *loss3) {
     SPAI_CHECK(B >= 1, SPAI_ERR_INVALID, "train_batch: empty batch");
@@ -1813,7 +1801,7 @@ int learner_train_batch(spai_learner *L, uint32_t B, const float *states, const 
     float *terms = L->stage + nin + 2;   // the staged inputs were consumed by the DMA above (stream order)
     SPAI_HIP(hipMemcpyAsync(terms, L->loss_terms.p, (size_t)B * 2 * 4, hipMemcpyDeviceToHost, st));
     SPAI_HIP(hipStreamSynchronize(st));
-    if (loss3) sum_loss(terms, B, loss3);
+    (void)lc::sum_loss(terms, B, loss3);
     return SPAI_OK;
 }
 
@@ -1847,37 +1835,17 @@ int learner_train_batches(spai_learner *L, uint32_t k, uint32_t B, const float *
     }
     SPAI_HIP(hipStreamSynchronize(st));
     if (losses)
-        for (uint32_t j = 0; j < k; ++j) sum_loss(L->terms_host + (size_t)j * B * 2, B, losses + 3 * j);
+        for (uint32_t j = 0; j < k; ++j) (void)lc::sum_loss(L->terms_host + (size_t)j * B * 2, B, losses + 3 * j);
     return SPAI_OK;
 }
 
-// Model::train (model/mod.rs:100-149): a fresh Adam (the reference builds the
-// optimizer inside train), one permutation of the n samples (Tensor::randperm,
-// here a Philox-keyed Fisher-Yates), then `epochs` passes of ceil(n / batch)
-// train steps over the permuted samples (the last batch may be short).
+// Model::train: lc::train_epochs (learner_common.h) over learner_train_batch
 int learner_train_epochs(spai_learner *L, uint32_t n, const float *states, const float *policies,
                          const float *values, uint32_t epochs, uint32_t batch, uint64_t seed, float *loss3) {
-    SPAI_CHECK(n >= 1 && batch >= 1, SPAI_ERR_INVALID, "train: need samples and a batch size");
-    hipStream_t st = L->eng->stream;
-    SPAI_HIP(hipMemsetAsync(L->m.p, 0, L->n_params * 4, st));   // Adam::default().build(..) per call
-    SPAI_HIP(hipMemsetAsync(L->v.p, 0, L->n_params * 4, st));
-    L->step = 0;
-    std::vector<uint32_t> perm;
-    choose_multiple(n, n, seed, 0x7EA1Bull, perm);   // a full random permutation
-    std::vector<float> s((size_t)batch * 126), p((size_t)batch * 7), v(batch);
-    const uint32_t nb = (n + batch - 1) / batch;
-    for (uint32_t ep = 0; ep < epochs; ++ep)
-        for (uint32_t b = 0; b < nb; ++b) {
-            const uint32_t lo = b * batch, m = std::min(batch, n - lo);
-            for (uint32_t i = 0; i < m; ++i) {
-                const uint32_t j = perm[lo + i];
-                memcpy(&s[(size_t)i * 126], states + (size_t)j * 126, 126 * 4);
-                memcpy(&p[(size_t)i * 7], policies + (size_t)j * 7, 7 * 4);
-                v[i] = values[j];
-            }
-            SPAI_TRY(learner_train_batch(L, m, s.data(), p.data(), v.data(), loss3));
-        }
-    return SPAI_OK;
+    return lc::train_epochs(*L, L->eng->stream, 3 * kCells, 7, n, states, policies, values, epochs, batch, seed,
+                            [&](uint32_t m, const float *s, const float *p, const float *v) {
+                                return learner_train_batch(L, m, s, p, v, loss3);
+                            });
 }
 
 int learner_params(spai_learner *L, float *params, size_t n, bool grads) {

@@ -36,6 +36,23 @@ void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
         if (rc_ != SPAI_OK) return rc_; \
     } while (0)
 
+// entry-point argument checks: a required pointer; the handle's device made current
+#define SPAI_PTR(p)                                            \
+    do {                                                       \
+        if (!(p)) {                                            \
+            ::spai::set_error("%s must not be NULL", #p);      \
+            return SPAI_ERR_INVALID;                           \
+        }                                                      \
+    } while (0)
+
+#define SPAI_SET_DEVICE(e)                                                 \
+    do {                                                                   \
+        if (hipSetDevice((e)->device) != hipSuccess) {                     \
+            ::spai::set_error("hipSetDevice(%d) failed", (e)->device);     \
+            return SPAI_ERR_DEVICE;                                        \
+        }                                                                  \
+    } while (0)
+
 template <class T>
 struct DevBuf {
     T *p = nullptr;

@@ -515,23 +515,10 @@ void visit_policy(const State &root, const uint32_t *st, float *pol, uint32_t *i
 using namespace spai;
 using namespace spai::ttt;
 
-#define T_CHECK(e)                                                    \
-    do {                                                              \
-        if (!(e)) {                                                   \
-            set_error("null handle");                                 \
-            return SPAI_ERR_INVALID;                                  \
-        }                                                             \
-        if (hipSetDevice((e)->device) != hipSuccess) {                \
-            set_error("hipSetDevice(%d) failed", (e)->device);        \
-            return SPAI_ERR_DEVICE;                                   \
-        }                                                             \
-    } while (0)
-#define T_PTR(p)                                                      \
-    do {                                                              \
-        if (!(p)) {                                                   \
-            set_error("%s must not be NULL", #p);                     \
-            return SPAI_ERR_INVALID;                                  \
-        }                                                             \
+#define T_CHECK(e)                                          \
+    do {                                                    \
+        SPAI_CHECK(e, SPAI_ERR_INVALID, "null handle");     \
+        SPAI_SET_DEVICE(e);                                 \
     } while (0)
 
 static State ttt_from_abi(const spai_ttt_state &s) { return State{s.x, s.o, s.num_actions_played, s.status}; }
@@ -564,8 +551,8 @@ static int slots_op(spai_ttt *e, uint32_t first, uint32_t n, int op, const int32
 extern "C" {
 
 int spai_ttt_create(const spai_config *cfg, int device, spai_ttt **out) {
-    T_PTR(cfg);
-    T_PTR(out);
+    SPAI_PTR(cfg);
+    SPAI_PTR(out);
     SPAI_CHECK(cfg->eval <= SPAI_EVAL_HASH, SPAI_ERR_INVALID, "bad eval kind %u", cfg->eval);
     SPAI_CHECK(cfg->max_trees >= 1 && cfg->num_searches >= 1 && cfg->num_searches <= (1u << 20), SPAI_ERR_INVALID,
                "max_trees and num_searches must be >= 1");
@@ -672,14 +659,14 @@ int spai_ttt_mask_invalid(spai_ttt *e, uint32_t first, uint32_t n, const float *
 }
 
 int spai_ttt_net_num_params(int blocks, size_t *count) {
-    T_PTR(count);
+    SPAI_PTR(count);
     *count = num_params(blocks);
     return SPAI_OK;
 }
 
 // tch 0.13 default init (as spai_net_init_params), Philox keyed by (seed, tensor, index)
 int spai_ttt_net_init_params(int blocks, uint64_t seed, float *params) {
-    T_PTR(params);
+    SPAI_PTR(params);
     uint32_t t = 0;
     float *p = params;
     auto uni = [&](size_t n, float lo, float hi) {
@@ -717,8 +704,8 @@ int spai_ttt_net_init_params(int blocks, uint64_t seed, float *params) {
 
 int spai_ttt_net_create(spai_ttt *e, int blocks, const float *params, size_t n, spai_ttt_net **out) {
     T_CHECK(e);
-    T_PTR(out);
-    T_PTR(params);
+    SPAI_PTR(out);
+    SPAI_PTR(params);
     SPAI_CHECK(blocks >= 0 && blocks <= kMaxBlocks, SPAI_ERR_UNSUPPORTED, "ttt net: 0..%d blocks", kMaxBlocks);
     SPAI_CHECK(n == num_params(blocks), SPAI_ERR_INVALID, "expected %zu params, got %zu", num_params(blocks), n);
     std::vector<float> wt, b;
@@ -777,12 +764,12 @@ int spai_ttt_net_destroy(spai_ttt_net *net) {
 }
 
 int spai_ttt_net_forward(spai_ttt_net *net, uint32_t n, const float *x, float *logits, float *value) {
-    T_PTR(net);
+    SPAI_PTR(net);
     T_CHECK(net->eng);
     if (!n) return SPAI_OK;
-    T_PTR(x);
-    T_PTR(logits);
-    T_PTR(value);
+    SPAI_PTR(x);
+    SPAI_PTR(logits);
+    SPAI_PTR(value);
     spai_ttt *e = static_cast<spai_ttt *>(net->eng);
     if (net->io_cap < n) {
         SPAI_TRY(net->io_x.alloc((size_t)n * 27));
@@ -801,14 +788,14 @@ int spai_ttt_net_forward(spai_ttt_net *net, uint32_t n, const float *x, float *l
 
 // Model::predict (model/mod.rs:36-98) over game slots [first, first+n)
 int spai_ttt_predict(spai_ttt_net *net, uint32_t first, uint32_t n, float *priors, float *values) {
-    T_PTR(net);
+    SPAI_PTR(net);
     T_CHECK(net->eng);
     spai_ttt *e = static_cast<spai_ttt *>(net->eng);
     SPAI_CHECK((uint64_t)first + n <= e->n_slots, SPAI_ERR_INVALID, "slots [%u, %u) out of range (%u)", first,
                first + n, e->n_slots);
     if (!n) return SPAI_OK;
-    T_PTR(priors);
-    T_PTR(values);
+    SPAI_PTR(priors);
+    SPAI_PTR(values);
     if (net->io_cap < n) {
         SPAI_TRY(net->io_x.alloc((size_t)n * 27));
         SPAI_TRY(net->io_l.alloc((size_t)n * 9));
@@ -841,7 +828,7 @@ int spai_ttt_trees_create(spai_ttt *e, uint32_t n) {
 int spai_ttt_search(spai_ttt *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, float *policy,
                     uint32_t *child_ids, float *child_visits, uint32_t *n_children) {
     T_CHECK(e);
-    T_PTR(tree_idx);
+    SPAI_PTR(tree_idx);
     SPAI_CHECK(e->n_trees > 0 && n >= 1 && n <= e->n_trees, SPAI_ERR_INVALID, "search: n=%u trees (have %u)", n,
                e->n_trees);
     SPAI_CHECK(num_searches <= e->cfg.num_searches, SPAI_ERR_INVALID, "num_searches > cfg.num_searches");
@@ -862,7 +849,7 @@ int spai_ttt_search(spai_ttt *e, uint32_t n, const uint32_t *tree_idx, uint32_t 
 
 int spai_ttt_tree_reset(spai_ttt *e, uint32_t tree, const spai_ttt_state *root) {
     T_CHECK(e);
-    T_PTR(root);
+    SPAI_PTR(root);
     SPAI_CHECK(tree < e->n_trees, SPAI_ERR_INVALID, "tree %u out of range (%u trees)", tree, e->n_trees);
     const State st = ttt_from_abi(*root);
     SPAI_CHECK(!(st.x & st.o) && st.x <= kFull && st.o <= kFull && st.status <= SPAI_WON, SPAI_ERR_INVALID,

@@ -1,6 +1,7 @@
 // ttt_engine.h — the TicTacToe engine and net handles (ttt.hip), shared with
-// the TicTacToe learner (ttt_learner.hip), which runs on the engine's device
-// and stream and refreshes a net's weights in place.
+// the TicTacToe learner (ttt_learner.hip on learner_common.h's shared core),
+// which runs on the engine's device and stream and refreshes a net's weights
+// in place.
 #pragma once
 #include "spai_internal.h"
 

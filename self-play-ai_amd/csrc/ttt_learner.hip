@@ -29,25 +29,31 @@
 // 16x16 tile of dW for one tap and sums all 9B rows in order inside its MFMA
 // accumulator.  Linear gradients: one thread per entry, samples in order.
 // Loss: per-sample terms, summed on the host in order.
-#include <algorithm>
+//
+// This file holds what is TicTacToe's: the conv, weight-gradient and head
+// kernels, the step's launch chain and the entry points.  The BatchNorm and Adam
+// kernels (k_lc_bn_fwd<9>, k_lc_bn_bwd<9>, k_lc_adam), the learner's state, the
+// staged train step and Model::train's epoch loop are learner_common.h's, shared
+// with chess_learner.hip.
 #include <cmath>
-#include <cstring>
 #include <new>
 #include <vector>
 
-#include "spai_internal.h"
+#include "learner_common.h"
 #include "ttt_engine.h"
 
 namespace spai {
 namespace ttt {
 namespace {
 
+using lc::Conv;
+using lc::kBnThreads;
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kPolC = 32, kValC = 3;
 constexpr int kPolK = kPolC * kCells;   // 288
 constexpr int kValK = kValC * kCells;   // 27
-constexpr int kBnThreads = 256;
 
 // 3x3 conv (pad 1) as an implicit GEMM, out[row][n] = sum_kk A[row][kk] Bm[kk][n],
 // kk = channel*9 + tap, one wave per (M-tile = blockIdx.x, N-tile = wave).
@@ -120,103 +126,6 @@ __global__ __launch_bounds__(64) void k_tl_wgrad(const float *__restrict__ dz, i
     for (int r = 0; r < 4; ++r) {
         const int oco = ct * 16 + 4 * lk + r;
         if (oco < cout && ci < cin) dw[((size_t)oco * cin + ci) * 9 + tap] = acc[r];
-    }
-}
-
-// the workgroup's sum in a fixed order (every thread gets it)
-__device__ __forceinline__ float block_sum(float v, float *sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int o = kBnThreads / 2; o > 0; o >>= 1) {
-        if (t < o) sh[t] = sh[t] + sh[t + o];
-        __syncthreads();
-    }
-    const float r = sh[0];
-    __syncthreads();
-    return r;
-}
-
-// train-mode BatchNorm of channel blockIdx.x over the 9B values z[:, c, :]: batch
-// mean and biased variance, a = relu(gamma xhat + beta (+ res)), and the running
-// statistics (momentum, unbiased variance)
-__global__ __launch_bounds__(kBnThreads) void k_tl_bn_fwd(const float *__restrict__ z, int C, int B,
-                                                          const float *__restrict__ gamma,
-                                                          const float *__restrict__ beta, float *__restrict__ run_mu,
-                                                          float *__restrict__ run_var, const float *__restrict__ res,
-                                                          float *__restrict__ a, float *__restrict__ mean_out,
-                                                          float *__restrict__ invstd_out, float momentum, float eps) {
-    __shared__ float sh[kBnThreads];
-    const int c = blockIdx.x, t = threadIdx.x, nn = kCells * B;
-    float acc = 0.0f;
-    for (int i = t; i < nn; i += kBnThreads) {
-        const int s = i / kCells;
-        acc += z[((size_t)s * C + c) * kCells + (i - kCells * s)];
-    }
-    const float mean = block_sum(acc, sh) / (float)nn;
-    acc = 0.0f;
-    for (int i = t; i < nn; i += kBnThreads) {
-        const int s = i / kCells;
-        const float d = z[((size_t)s * C + c) * kCells + (i - kCells * s)] - mean;
-        acc += d * d;
-    }
-    const float var = block_sum(acc, sh) / (float)nn;
-    const float invstd = 1.0f / sqrtf(var + eps);
-    const float g = gamma[c], be = beta[c];
-    for (int i = t; i < nn; i += kBnThreads) {
-        const int s = i / kCells;
-        const size_t idx = ((size_t)s * C + c) * kCells + (i - kCells * s);
-        float yv = g * ((z[idx] - mean) * invstd) + be;
-        if (res) yv += res[idx];
-        a[idx] = fmaxf(yv, 0.0f);
-    }
-    if (t == 0) {
-        mean_out[c] = mean;
-        invstd_out[c] = invstd;
-        run_mu[c] = (1.0f - momentum) * run_mu[c] + momentum * mean;
-        run_var[c] = (1.0f - momentum) * run_var[c] + momentum * (var * ((float)nn / (float)(nn - 1)));
-    }
-}
-
-// backward of ReLU + BatchNorm for channel blockIdx.x: dy = da [a > 0];
-// dbeta = sum dy, dgamma = sum dy xhat, dz = gamma invstd / nn (nn dy - dbeta - xhat dgamma),
-// dbias = sum dz.  keep_dy: da becomes dy (the skip connection's gradient).
-__global__ __launch_bounds__(kBnThreads) void k_tl_bn_bwd(float *__restrict__ da, const float *__restrict__ a,
-                                                          const float *__restrict__ z, int C, int B,
-                                                          const float *__restrict__ mean,
-                                                          const float *__restrict__ invstd,
-                                                          const float *__restrict__ gamma, float *__restrict__ dz,
-                                                          float *__restrict__ g_gamma, float *__restrict__ g_beta,
-                                                          float *__restrict__ g_bias, int keep_dy) {
-    __shared__ float sh[kBnThreads];
-    const int c = blockIdx.x, t = threadIdx.x, nn = kCells * B;
-    const float mu = mean[c], is = invstd[c];
-    float sb = 0.0f, sg = 0.0f;
-    for (int i = t; i < nn; i += kBnThreads) {
-        const int s = i / kCells;
-        const size_t idx = ((size_t)s * C + c) * kCells + (i - kCells * s);
-        const float dy = a[idx] > 0.0f ? da[idx] : 0.0f;
-        sb += dy;
-        sg += dy * ((z[idx] - mu) * is);
-    }
-    sb = block_sum(sb, sh);
-    sg = block_sum(sg, sh);
-    const float k = gamma[c] * is / (float)nn;
-    float sz = 0.0f;
-    for (int i = t; i < nn; i += kBnThreads) {
-        const int s = i / kCells;
-        const size_t idx = ((size_t)s * C + c) * kCells + (i - kCells * s);
-        const float dy = a[idx] > 0.0f ? da[idx] : 0.0f;
-        const float v = k * ((float)nn * dy - sb - ((z[idx] - mu) * is) * sg);
-        dz[idx] = v;
-        if (keep_dy) da[idx] = dy;
-        sz += v;
-    }
-    sz = block_sum(sz, sh);
-    if (t == 0) {
-        g_gamma[c] = sg;
-        g_beta[c] = sb;
-        g_bias[c] = sz;
     }
 }
 
@@ -301,45 +210,16 @@ __global__ void k_tl_lin_grad(const float *__restrict__ dlogits, const float *__
     }
 }
 
-// Adam, torch semantics (as learner.hip): m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
-// p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps).  The BN running
-// statistics have gradient 0, so their moments stay 0 and they do not move.
-__global__ void k_tl_adam(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
-                          float *__restrict__ v, size_t n, float lr, float b1, float b2, float eps, float bc1,
-                          float bc2_sqrt) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float gi = g[i];
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    p[i] -= (lr / bc1) * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-}
-
-struct Conv {
-    int ci, co;
-    size_t w, b, g, be, mu, var;   // offsets into the flat parameter vector
-};
-
 }  // namespace
 
-struct Learner {
-    spai_ttt *eng = nullptr;
+struct Learner : lc::Core {   // batch_in: [x: B*27 | pi: B*9 | z: B]
     int blocks = 0;
-    spai_adam_config cfg{};
-    uint64_t step = 0;
-    uint32_t max_batch = 0, last_batch = 0;
-    size_t n_params = 0;
     std::vector<Conv> convs;   // stem, 2*blocks residual, policy conv, value conv
     size_t pol_w = 0, pol_b = 0, val_w = 0, val_b = 0;
-    DevBuf<float> p, g, m, v;              // parameters, gradients, Adam moments (flat)
-    DevBuf<float> batch_in;                // [x: B*27 | pi: B*9 | z: B]
-    float *stage = nullptr;                // its pinned host copy, then the loss terms [B*2]
     std::vector<DevBuf<float>> z, a;       // per conv layer: pre-BN output, post-ReLU activation
     DevBuf<float> stat;                    // per conv layer: batch mean [64] | inverse std [64]
     DevBuf<float> g0, g1, dz;              // backward: two activation-gradient buffers and dz, [B][64][9]
-    DevBuf<float> dlogits, dpre, terms;
+    DevBuf<float> dlogits;
 };
 
 }  // namespace ttt
@@ -354,9 +234,7 @@ namespace {
 
 int alloc_batch(spai_ttt_learner *L, uint32_t B) {
     if (B <= L->max_batch) return SPAI_OK;
-    SPAI_HIP(hipStreamSynchronize(L->eng->stream));   // nothing in flight reads the old buffers
-    L->max_batch = 0;
-    L->last_batch = 0;
+    SPAI_TRY(lc::core_grow_batch(*L, B));
     const size_t nl = L->convs.size();
     for (size_t l = 0; l < nl; ++l) {
         SPAI_TRY(L->z[l].alloc((size_t)B * L->convs[l].co * kCells));
@@ -366,12 +244,6 @@ int alloc_batch(spai_ttt_learner *L, uint32_t B) {
     SPAI_TRY(L->g1.alloc((size_t)B * kHid * kCells));
     SPAI_TRY(L->dz.alloc((size_t)B * kHid * kCells));
     SPAI_TRY(L->dlogits.alloc((size_t)B * kCells));
-    SPAI_TRY(L->dpre.alloc(B));
-    SPAI_TRY(L->terms.alloc((size_t)B * 2));
-    SPAI_TRY(L->batch_in.alloc((size_t)B * 37));
-    if (L->stage) (void)hipHostFree(L->stage);
-    L->stage = nullptr;
-    SPAI_HIP(hipHostMalloc((void **)&L->stage, (size_t)B * 39 * sizeof(float), hipHostMallocDefault));
     L->max_batch = B;
     return SPAI_OK;
 }
@@ -381,8 +253,9 @@ void conv_fwd(spai_ttt_learner *L, int l, const float *in, const float *res, int
     const int M = kCells * B, mt = (M + 15) / 16, nt = (c.co + 15) / 16;
     float *P = L->p.p, *stat = L->stat.p + (size_t)l * 2 * kHid;
     k_tl_conv<0><<<mt, 64 * nt, 0, st>>>(in, c.ci, P + c.w, P + c.b, nullptr, L->z[l].p, c.co, M);
-    k_tl_bn_fwd<<<c.co, kBnThreads, 0, st>>>(L->z[l].p, c.co, B, P + c.g, P + c.be, P + c.mu, P + c.var, res,
-                                             L->a[l].p, stat, stat + kHid, L->cfg.bn_momentum, L->cfg.bn_eps);
+    lc::k_lc_bn_fwd<kCells><<<c.co, kBnThreads, 0, st>>>(L->z[l].p, c.co, B, P + c.g, P + c.be, P + c.mu, P + c.var,
+                                                         res, L->a[l].p, stat, stat + kHid, L->cfg.bn_momentum,
+                                                         L->cfg.bn_eps);
 }
 
 // da: gradient of layer l's activation (becomes dy when keep_dy); in: the layer's input
@@ -392,8 +265,8 @@ void conv_bwd(spai_ttt_learner *L, int l, float *da, int keep_dy, const float *i
     const Conv &c = L->convs[l];
     const int M = kCells * B;
     float *P = L->p.p, *G = L->g.p, *stat = L->stat.p + (size_t)l * 2 * kHid;
-    k_tl_bn_bwd<<<c.co, kBnThreads, 0, st>>>(da, L->a[l].p, L->z[l].p, c.co, B, stat, stat + kHid, P + c.g, L->dz.p,
-                                             G + c.g, G + c.be, G + c.b, keep_dy);
+    lc::k_lc_bn_bwd<kCells><<<c.co, kBnThreads, 0, st>>>(da, L->a[l].p, L->z[l].p, c.co, B, stat, stat + kHid, P + c.g,
+                                                         L->dz.p, G + c.g, G + c.be, G + c.b, keep_dy);
     k_tl_wgrad<<<dim3(((c.co + 15) / 16) * ((c.ci + 15) / 16), 9), 64, 0, st>>>(L->dz.p, c.co, in, c.ci, G + c.w, M);
     if (dx)
         k_tl_conv<1><<<(M + 15) / 16, 64 * ((c.ci + 15) / 16), 0, st>>>(L->dz.p, c.co, P + c.w, nullptr, addend, dx,
@@ -402,7 +275,7 @@ void conv_bwd(spai_ttt_learner *L, int l, float *da, int keep_dy, const float *i
 
 // one train step on the batch already in batch_in
 int enqueue_step(spai_ttt_learner *L, int B) {
-    hipStream_t st = L->eng->stream;
+    hipStream_t st = L->stream;
     float *P = L->p.p, *G = L->g.p;
     const float *x = L->batch_in.p, *pi = x + (size_t)B * 27, *zt = pi + (size_t)B * kCells;
     const int nb = L->blocks, lp = 2 * nb + 1, lv = lp + 1;
@@ -428,12 +301,7 @@ int enqueue_step(spai_ttt_learner *L, int B) {
         conv_bwd(L, 1 + 2 * k, oth, 0, L->a[2 * k].p, cur, cur, B, st);
     }
     conv_bwd(L, 0, cur, 0, x, nullptr, nullptr, B, st);
-    L->step += 1;
-    const double t = (double)L->step;
-    const float bc1 = (float)(1.0 - std::pow((double)L->cfg.beta1, t));
-    const float bc2 = (float)std::sqrt(1.0 - std::pow((double)L->cfg.beta2, t));
-    k_tl_adam<<<(unsigned)((L->n_params + 255) / 256), 256, 0, st>>>(P, G, L->m.p, L->v.p, L->n_params, L->cfg.lr,
-                                                                      L->cfg.beta1, L->cfg.beta2, L->cfg.eps, bc1, bc2);
+    lc::adam_step(*L);
     SPAI_HIP(hipGetLastError());
     L->last_batch = (uint32_t)B;
     return SPAI_OK;
@@ -443,112 +311,52 @@ int train_batch(spai_ttt_learner *L, uint32_t B, const float *states, const floa
                 float *loss3) {
     SPAI_CHECK(B >= 1 && B <= (1u << 20), SPAI_ERR_INVALID, "train_batch: batch of %u samples", B);
     SPAI_TRY(alloc_batch(L, B));
-    hipStream_t st = L->eng->stream;
-    memcpy(L->stage, states, (size_t)B * 27 * 4);
-    memcpy(L->stage + (size_t)B * 27, policies, (size_t)B * kCells * 4);
-    memcpy(L->stage + (size_t)B * 36, values, (size_t)B * 4);
-    SPAI_HIP(hipMemcpyAsync(L->batch_in.p, L->stage, (size_t)B * 37 * 4, hipMemcpyHostToDevice, st));
-    SPAI_TRY(enqueue_step(L, (int)B));
-    float *terms = L->stage + (size_t)B * 37;
-    SPAI_HIP(hipMemcpyAsync(terms, L->terms.p, (size_t)B * 2 * 4, hipMemcpyDeviceToHost, st));
-    SPAI_HIP(hipStreamSynchronize(st));
-    if (loss3) {   // the fixed-order host sums of the step's loss terms
-        double lp = 0, lv = 0;
-        for (uint32_t b = 0; b < B; ++b) {
-            lp += terms[2 * b];
-            lv += terms[2 * b + 1];
-        }
-        loss3[1] = (float)(lp / B);
-        loss3[2] = (float)(lv / B);
-        loss3[0] = loss3[1] + loss3[2];
-    }
-    return SPAI_OK;
+    return lc::train_batch(*L, B, states, policies, values, loss3, nullptr, [&](int b) { return enqueue_step(L, b); });
 }
 
 void learner_free(spai_ttt_learner *L) {
     for (auto &d : L->z) d.release();
     for (auto &d : L->a) d.release();
-    for (auto *d : {&L->p, &L->g, &L->m, &L->v, &L->batch_in, &L->stat, &L->g0, &L->g1, &L->dz, &L->dlogits, &L->dpre,
-                    &L->terms})
-        d->release();
-    if (L->stage) (void)hipHostFree(L->stage);
+    for (auto *d : {&L->stat, &L->g0, &L->g1, &L->dz, &L->dlogits}) d->release();
+    lc::core_free(*L);
     delete L;
 }
 
 int learner_init(spai_ttt_learner *L, const float *params) {
-    size_t off = 0;
-    auto conv = [&](int ci, int co) {
-        Conv c{};
-        c.ci = ci;
-        c.co = co;
-        c.w = off;
-        off += (size_t)co * ci * 9;
-        c.b = off;
-        c.g = off + co;
-        c.be = off + 2 * co;
-        c.mu = off + 3 * co;
-        c.var = off + 4 * co;
-        off += 5 * (size_t)co;
-        L->convs.push_back(c);
-    };
-    conv(3, kHid);
-    for (int i = 0; i < 2 * L->blocks; ++i) conv(kHid, kHid);
-    conv(kHid, kPolC);
-    L->pol_w = off;
-    L->pol_b = off + (size_t)kCells * kPolK;
-    off += (size_t)kCells * kPolK + kCells;
-    conv(kHid, kValC);
-    L->val_w = off;
-    L->val_b = off + kValK;
-    off += kValK + 1;
-    SPAI_CHECK(off == L->n_params, SPAI_ERR_INVALID, "ttt learner layout: %zu != %zu", off, L->n_params);
-    const size_t n = L->n_params, nl = L->convs.size();
+    lc::Layout lay;
+    L->convs.push_back(lay.conv3x3_bn(3, kHid));
+    for (int i = 0; i < 2 * L->blocks; ++i) L->convs.push_back(lay.conv3x3_bn(kHid, kHid));
+    L->convs.push_back(lay.conv3x3_bn(kHid, kPolC));
+    L->pol_w = lay.take((size_t)kCells * kPolK);
+    L->pol_b = lay.take(kCells);
+    L->convs.push_back(lay.conv3x3_bn(kHid, kValC));
+    L->val_w = lay.take(kValK);
+    L->val_b = lay.take(1);
+    SPAI_CHECK(lay.off == L->n_params, SPAI_ERR_INVALID, "ttt learner layout: %zu != %zu", lay.off, L->n_params);
+    const size_t nl = L->convs.size();
     L->z.resize(nl);
     L->a.resize(nl);
-    hipStream_t st = L->eng->stream;
-    for (auto *d : {&L->p, &L->g, &L->m, &L->v}) SPAI_TRY(d->alloc(n));
     SPAI_TRY(L->stat.alloc(nl * 2 * kHid));
-    SPAI_HIP(hipMemcpyAsync(L->p.p, params, n * 4, hipMemcpyHostToDevice, st));
-    for (auto *d : {&L->g, &L->m, &L->v}) SPAI_HIP(hipMemsetAsync(d->p, 0, n * 4, st));
-    SPAI_HIP(hipStreamSynchronize(st));   // params is the caller's
-    return SPAI_OK;
+    return lc::core_init(*L, params);
 }
 
 }  // namespace
-
-#define TL_PTR(p)                                                     \
-    do {                                                              \
-        if (!(p)) {                                                   \
-            set_error("%s must not be NULL", #p);                     \
-            return SPAI_ERR_INVALID;                                  \
-        }                                                             \
-    } while (0)
-#define TL_DEVICE(e)                                                  \
-    do {                                                              \
-        if (hipSetDevice((e)->device) != hipSuccess) {                \
-            set_error("hipSetDevice(%d) failed", (e)->device);        \
-            return SPAI_ERR_DEVICE;                                   \
-        }                                                             \
-    } while (0)
 
 extern "C" {
 
 int spai_ttt_learner_create(spai_ttt *e, int blocks, const float *params, size_t n_params,
                             const spai_adam_config *cfg, spai_ttt_learner **out) {
-    TL_PTR(e);
-    TL_PTR(params);
-    TL_PTR(out);
+    SPAI_PTR(e);
+    SPAI_PTR(params);
+    SPAI_PTR(out);
     SPAI_CHECK(blocks >= 0 && blocks <= kMaxBlocks, SPAI_ERR_UNSUPPORTED, "ttt learner: 0..%d blocks", kMaxBlocks);
     SPAI_CHECK(n_params == num_params(blocks), SPAI_ERR_INVALID, "expected %zu params, got %zu", num_params(blocks),
                n_params);
-    TL_DEVICE(e);
+    SPAI_SET_DEVICE(e);
     spai_ttt_learner *L = new (std::nothrow) spai_ttt_learner();
     SPAI_CHECK(L, SPAI_ERR_INVALID, "out of host memory");
-    L->eng = e;
+    lc::core_setup(*L, e->device, e->stream, n_params, cfg, 3 * kCells, kCells);
     L->blocks = blocks;
-    L->n_params = n_params;
-    if (cfg) L->cfg = *cfg;
-    else (void)spai_adam_config_default(&L->cfg);
     const int rc = learner_init(L, params);
     if (rc != SPAI_OK) {
         learner_free(L);
@@ -560,95 +368,67 @@ int spai_ttt_learner_create(spai_ttt *e, int blocks, const float *params, size_t
 
 int spai_ttt_learner_destroy(spai_ttt_learner *L) {
     if (!L) return SPAI_OK;
-    (void)hipSetDevice(L->eng->device);
-    (void)hipStreamSynchronize(L->eng->stream);
+    (void)hipSetDevice(L->device);
+    (void)hipStreamSynchronize(L->stream);
     learner_free(L);
     return SPAI_OK;
 }
 
 int spai_ttt_learner_train_batch(spai_ttt_learner *L, uint32_t n, const float *states, const float *policies,
                                  const float *values, float *loss) {
-    TL_PTR(L);
-    TL_PTR(states);
-    TL_PTR(policies);
-    TL_PTR(values);
-    TL_DEVICE(L->eng);
+    SPAI_PTR(L);
+    SPAI_PTR(states);
+    SPAI_PTR(policies);
+    SPAI_PTR(values);
+    SPAI_SET_DEVICE(L);
     return train_batch(L, n, states, policies, values, loss);
 }
 
-// Model::train (model/mod.rs:100-149): a fresh Adam (the reference builds the optimizer
-// inside train), one permutation of the n samples, then `epochs` passes of
-// ceil(n / batch) train steps over the permuted samples (the last batch may be short)
+// Model::train: lc::train_epochs over this learner's train step
 int spai_ttt_learner_train(spai_ttt_learner *L, uint32_t n, const float *states, const float *policies,
                            const float *values, uint32_t epochs, uint32_t batch, uint64_t seed, float *loss) {
-    TL_PTR(L);
-    TL_PTR(states);
-    TL_PTR(policies);
-    TL_PTR(values);
-    TL_DEVICE(L->eng);
-    SPAI_CHECK(n >= 1 && batch >= 1, SPAI_ERR_INVALID, "train: need samples and a batch size");
-    hipStream_t st = L->eng->stream;
-    SPAI_HIP(hipMemsetAsync(L->m.p, 0, L->n_params * 4, st));
-    SPAI_HIP(hipMemsetAsync(L->v.p, 0, L->n_params * 4, st));
-    L->step = 0;
-    std::vector<uint32_t> perm;
-    choose_multiple(n, n, seed, 0x7EA1Bull, perm);
-    std::vector<float> s((size_t)batch * 27), p((size_t)batch * kCells), v(batch);
-    const uint32_t nb = (n + batch - 1) / batch;
-    for (uint32_t ep = 0; ep < epochs; ++ep)
-        for (uint32_t b = 0; b < nb; ++b) {
-            const uint32_t lo = b * batch, m = std::min(batch, n - lo);
-            for (uint32_t i = 0; i < m; ++i) {
-                const uint32_t j = perm[lo + i];
-                memcpy(&s[(size_t)i * 27], states + (size_t)j * 27, 27 * 4);
-                memcpy(&p[(size_t)i * kCells], policies + (size_t)j * kCells, kCells * 4);
-                v[i] = values[j];
-            }
-            SPAI_TRY(train_batch(L, m, s.data(), p.data(), v.data(), loss));
-        }
-    return SPAI_OK;
-}
-
-static int read_flat(spai_ttt_learner *L, const float *src, float *dst, size_t n) {
-    SPAI_CHECK(n == L->n_params, SPAI_ERR_INVALID, "expected %zu params, got %zu", L->n_params, n);
-    hipStream_t st = L->eng->stream;
-    SPAI_HIP(hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToHost, st));
-    SPAI_HIP(hipStreamSynchronize(st));
-    return SPAI_OK;
+    SPAI_PTR(L);
+    SPAI_PTR(states);
+    SPAI_PTR(policies);
+    SPAI_PTR(values);
+    SPAI_SET_DEVICE(L);
+    return lc::train_epochs(*L, L->stream, L->xw, L->pw, n, states, policies, values, epochs, batch, seed,
+                            [&](uint32_t m, const float *s, const float *p, const float *v) {
+                                return train_batch(L, m, s, p, v, loss);
+                            });
 }
 
 int spai_ttt_learner_params(spai_ttt_learner *L, float *params, size_t n_params) {
-    TL_PTR(L);
-    TL_PTR(params);
-    TL_DEVICE(L->eng);
-    return read_flat(L, L->p.p, params, n_params);
+    SPAI_PTR(L);
+    SPAI_PTR(params);
+    SPAI_SET_DEVICE(L);
+    return lc::read_flat(*L, L->p.p, params, n_params);
 }
 
 int spai_ttt_learner_grads(spai_ttt_learner *L, float *grads, size_t n_params) {
-    TL_PTR(L);
-    TL_PTR(grads);
-    TL_DEVICE(L->eng);
-    return read_flat(L, L->g.p, grads, n_params);
+    SPAI_PTR(L);
+    SPAI_PTR(grads);
+    SPAI_SET_DEVICE(L);
+    return lc::read_flat(*L, L->g.p, grads, n_params);
 }
 
 int spai_ttt_learner_activation(spai_ttt_learner *L, int layer, float *out, size_t n) {
-    TL_PTR(L);
-    TL_PTR(out);
-    TL_DEVICE(L->eng);
+    SPAI_PTR(L);
+    SPAI_PTR(out);
+    SPAI_SET_DEVICE(L);
     SPAI_CHECK(layer >= 0 && (size_t)layer < L->convs.size(), SPAI_ERR_INVALID, "layer %d of %zu", layer,
                L->convs.size());
     SPAI_CHECK(L->last_batch > 0, SPAI_ERR_INVALID, "no train step yet");
     const size_t want = (size_t)L->last_batch * L->convs[layer].co * kCells;
     SPAI_CHECK(n == want, SPAI_ERR_INVALID, "expected %zu activations, got %zu", want, n);
-    hipStream_t st = L->eng->stream;
-    SPAI_HIP(hipMemcpyAsync(out, L->a[layer].p, n * 4, hipMemcpyDeviceToHost, st));
-    SPAI_HIP(hipStreamSynchronize(st));
+    SPAI_HIP(hipMemcpyAsync(out, L->a[layer].p, n * 4, hipMemcpyDeviceToHost, L->stream));
+    SPAI_HIP(hipStreamSynchronize(L->stream));
     return SPAI_OK;
 }
 
 int spai_ttt_learner_last_batch(spai_ttt_learner *L, uint32_t *n) {
-    TL_PTR(L);
-    TL_PTR(n);
+    SPAI_PTR(L);
+    SPAI_PTR(n);
     *n = L->last_batch;
     return SPAI_OK;
 }
@@ -657,9 +437,9 @@ int spai_ttt_learner_last_batch(spai_ttt_learner *L, uint32_t *n) {
 // eval-mode BN in double, weights transposed to [ci*9 + tap][co]) into the net's own
 // allocations, stream-ordered behind whatever search still reads the old weights
 int spai_ttt_net_set_params(spai_ttt_net *net, const float *params, size_t n_params) {
-    TL_PTR(net);
-    TL_PTR(params);
-    TL_DEVICE(net->eng);
+    SPAI_PTR(net);
+    SPAI_PTR(params);
+    SPAI_SET_DEVICE(net->eng);
     SPAI_CHECK(n_params == num_params(net->blocks), SPAI_ERR_INVALID, "expected %zu params, got %zu",
                num_params(net->blocks), n_params);
     std::vector<float> wt, b;

@@ -17,6 +17,7 @@ import numpy as np
 
 import spai
 from spai import EVAL_HASH, EVAL_NET, EVAL_UNIFORM, GAME_CHESS, Config, SelfPlayStats, SpaiError  # noqa: F401
+from spai_learn import DeviceLearner, _iter_seed, _samples, learn_loop  # noqa: F401
 
 POLICY, ENC, MAX_MOVES = 4672, 1216, 256
 
@@ -409,65 +410,12 @@ class ChessNet:
         _check(lib().spai_chess_net_set_params(self.h, _p(p), p.size))
 
 
-class ChessLearner:
+class ChessLearner(DeviceLearner):
     """Device train step of the chess net (model/chess.rs under
     model/mod.rs:128-141) on the engine's device and stream, in exact fp32:
     train-mode forward, policy NLL + value MSE, backward, one Adam step.
     Mirrors spai_ttt.TTTLearner."""
-
-    def __init__(self, engine, blocks, params, **adam):
-        cfg = spai.AdamConfig()
-        _check(lib().spai_adam_config_default(C.byref(cfg)))
-        for k, v in adam.items():
-            setattr(cfg, k, float(v))
-        p = np.ascontiguousarray(params, np.float32)
-        self.n, self.blocks = p.size, blocks
-        self.eng = engine   # the learner runs on the engine's stream: keep it alive
-        h = C.c_void_p()
-        _check(lib().spai_chess_learner_create(engine.h, blocks, _p(p), p.size, C.byref(cfg), C.byref(h)))
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().spai_chess_learner_destroy(self.h)
-            self.h = None
-
-    @staticmethod
-    def _batch(states, policies, values):
-        x = np.ascontiguousarray(states, np.float32).reshape(-1, ENC)
-        pi = np.ascontiguousarray(policies, np.float32).reshape(-1, POLICY)
-        z = np.ascontiguousarray(values, np.float32).reshape(-1)
-        assert len(x) == len(pi) == len(z)
-        return x, pi, z
-
-    def train_batch(self, states, policies, values):
-        x, pi, z = self._batch(states, policies, values)
-        loss = np.zeros(3, np.float32)
-        _check(lib().spai_chess_learner_train_batch(self.h, len(z), _p(x), _p(pi), _p(z), _p(loss)))
-        return loss   # total, policy, value
-
-    def train(self, states, policies, values, epochs=1, batch=32, seed=0):
-        """Model::train (model/mod.rs:100-149): fresh Adam, one permutation, epochs x batches"""
-        x, pi, z = self._batch(states, policies, values)
-        loss = np.zeros(3, np.float32)
-        _check(lib().spai_chess_learner_train(self.h, len(z), _p(x), _p(pi), _p(z), epochs, batch, seed, _p(loss)))
-        return loss
-
-    def last_batch(self):
-        """the batch size of the latest train step (after train(): the last minibatch's)"""
-        n = C.c_uint32()
-        _check(lib().spai_chess_learner_last_batch(self.h, C.byref(n)))
-        return n.value
-
-    def params(self):
-        out = np.zeros(self.n, np.float32)
-        _check(lib().spai_chess_learner_params(self.h, _p(out), self.n))
-        return out
-
-    def grads(self):
-        out = np.zeros(self.n, np.float32)
-        _check(lib().spai_chess_learner_grads(self.h, _p(out), self.n))
-        return out
+    LIB, PREFIX, ENC, POLICY = staticmethod(lib), "spai_chess_learner", ENC, POLICY
 
     def activation(self, layer):
         """the last train step's post-ReLU activations: layers 0 .. 2*blocks the trunk
@@ -478,13 +426,6 @@ class ChessLearner:
         out = np.zeros(shape, np.float32)
         _check(lib().spai_chess_learner_activation(self.h, layer, _p(out), out.size))
         return out
-
-
-def _samples(games):
-    """self-play games (ascending game id) -> states [n][1216], policies [n][4672], values [n]"""
-    games = sorted(games, key=lambda g: g["game"])
-    return (np.concatenate([g["enc"] for g in games]), np.concatenate([g["policy"] for g in games]),
-            np.concatenate([g["value"] for g in games]))
 
 
 def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_games=100, batch_size=32, num_epochs=4,
@@ -503,45 +444,12 @@ def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_ga
     on_train_set(i, states, policies, values, game_ids) sees every training set.
     Returns per-iteration records: samples, loss [total, policy, value] of the last
     step, games, checkpoint."""
-    import os
-    P = np.ascontiguousarray(init_params(blocks, seed) if params is None else params, np.float32)
     G = num_parallel_self_play_games
-    eng = ChessEngine(num_searches=num_searches, max_trees=G if window is None else int(window), eval_kind=EVAL_NET,
-                      device=device, c=c, temperature=temperature, seed=seed, max_moves=max_moves)
-    net = ChessNet(eng, blocks, P)
-    eng.set_net(net)
-    L = ChessLearner(eng, blocks, P)
-    os.makedirs(checkpoint_dir, exist_ok=True)
-    out = []
-    try:
-        for i in range(num_learn_iters):
-            if i:
-                net.set_params(L.params())
-            batches = 1 if clone_self_play else num_self_play_iters
-            parts, gids, n_games = [], [], 0
-            for b in range(batches):
-                base = (i * num_self_play_iters + b) * G
-                games, _ = eng.self_play(G, game_id_base=base, window=window)
-                n_games += len(games)
-                parts.append(_samples(games))
-                gids.append(np.concatenate([np.full(g["n"], g["game"], np.int64)
-                                            for g in sorted(games, key=lambda g: g["game"])]))
-            if clone_self_play:
-                parts, gids = parts * num_self_play_iters, gids * num_self_play_iters
-            s, p, v = (np.concatenate([q[k] for q in parts]) for k in range(3))
-            if on_train_set is not None:
-                on_train_set(i, s, p, v, np.concatenate(gids))
-            loss = L.train(s, p, v, epochs=num_epochs, batch=batch_size, seed=_iter_seed(seed, i))
-            path = os.path.join(checkpoint_dir, f"{i}.safetensors")
-            spai.save_params(path, L.params(), blocks, 256, game=GAME_CHESS)   # spai_params_save_safetensors
-            out.append(dict(iteration=i, samples=int(len(v)), loss=[float(x) for x in loss], games=n_games,
-                            checkpoint=path))
-    finally:
-        L.close()
-        eng.close()
-    return out
-
-
-def _iter_seed(seed, i):
-    """the training permutation's seed of learn iteration i"""
-    return (int(seed) * 0x9E3779B97F4A7C15 + i + 1) & 0xFFFFFFFFFFFFFFFF
+    return learn_loop(
+        lambda: ChessEngine(num_searches=num_searches, max_trees=G if window is None else int(window),
+                            eval_kind=EVAL_NET, device=device, c=c, temperature=temperature, seed=seed,
+                            max_moves=max_moves),
+        lambda eng, P: ChessNet(eng, blocks, P), lambda eng, P: ChessLearner(eng, blocks, P),
+        init_params(blocks, seed) if params is None else params, blocks, 256, GAME_CHESS, num_learn_iters,
+        num_self_play_iters, G, batch_size, num_epochs, seed, checkpoint_dir, clone_self_play, on_train_set,
+        self_play_kw=dict(window=window))

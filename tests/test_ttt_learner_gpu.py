@@ -143,7 +143,7 @@ def test_ttt_learner_vs_restatement(st, blocks, B, steps):
 def test_ttt_learner_trained_like_vs_restatement(st, blocks, B, steps):
     """the same check from bf16_ref.trained_like parameters: conv biases, beta and the
     running mean away from 0, the running variance away from 1, gammas above 1 and
-    below 0, so the running-statistic blend and every factor of k_tl_bn_bwd count
+    below 0, so the running-statistic blend and every factor of k_lc_bn_bwd count
     (from init_params the old running mean is 0 and drops out of the blend).  The
     restatement is pinned to PyTorch float64 autograd from such parameters in
     tests/test_learner_ref_cpu.py.  The bars are the ones above, unchanged."""
