@@ -746,6 +746,12 @@ int spai_chess_match_set_one_stream(spai_chess *e, int on);
 /* root children of a tree without searching it (n = 0: root not expanded):
  * moves / visits [SPAI_CHESS_MAX_MOVES], zero past n; any output may be NULL */
 int spai_chess_tree_children(spai_chess *e, uint32_t tree, uint16_t *moves, uint32_t *visits, uint32_t *n);
+/* the same read with each child's whole node record, in stored (MoveGen) order: move, N, W and
+ * prior exactly as stored (n = 0: root not expanded).  Reads the tree's active half, so it holds
+ * after a compaction; it does not search and does not change the tree.
+ * moves / visits / value_sums / priors [SPAI_CHESS_MAX_MOVES], zero past n; any output may be NULL */
+int spai_chess_tree_child_stats(spai_chess *e, uint32_t tree, uint16_t *moves, uint32_t *visits, float *value_sums,
+                                float *priors, uint32_t *n);
 
 
 /* ---------------------------------------------------------------- tictactoe

@@ -320,6 +320,12 @@ int spai_chess_tree_children(spai_chess *e, uint32_t tree, uint16_t *moves, uint
     return tree_children(e, tree, moves, visits, n);
 }
 
+int spai_chess_tree_child_stats(spai_chess *e, uint32_t tree, uint16_t *moves, uint32_t *visits, float *value_sums,
+                                float *priors, uint32_t *n) {
+    CH_CHECK(e);
+    return tree_child_stats(e, tree, moves, visits, value_sums, priors, n);
+}
+
 int spai_chess_match_set_one_stream(spai_chess *e, int on) {
     CH_CHECK(e);
     return match_set_one_stream(e, on);

@@ -159,6 +159,9 @@ int tree_reset_from_slot(spai_chess *e, uint32_t tree, uint32_t slot);
 int tree_root(spai_chess *e, uint32_t tree, spai_chess_state *root, uint32_t *visits, float *value_sum);
 // moves / visits [kMaxMoves] (zero past *n), any of them null
 int tree_children(spai_chess *e, uint32_t tree, uint16_t *moves, uint32_t *visits, uint32_t *n);
+// the root children's node records (move, N, W, prior as stored), [kMaxMoves] each (zero past *n), any of them null
+int tree_child_stats(spai_chess *e, uint32_t tree, uint16_t *moves, uint32_t *visits, float *value_sums, float *priors,
+                     uint32_t *n);
 int trees_advance(spai_chess *e, uint32_t n, const uint32_t *tree_idx, const uint32_t *child_index, uint8_t *status,
                   uint32_t *reps);
 int selfplay_run(spai_chess *e, uint32_t n_games, uint64_t gid_base, spai_chess_sample_sink sink, void *user,

@@ -156,8 +156,10 @@ __global__ void __launch_bounds__(64) k_slots_mask(const Board *__restrict__ boa
 }
 
 // Model::predict's tail (model/mod.rs:62-93): softmax(-1) over the 4672 logits
-// (same reduction order as k_cexpand, so predict and search see the same
-// priors), then mask_invalid_actions.
+// in k_cexpand's reduction order, then mask_invalid_actions.  k_cexpand
+// renormalises with masked_normalize's fold over the legal entries, so predict
+// and the search see the same priors bit for bit
+// (tests/test_chess_search_net_gpu.py).
 __global__ void __launch_bounds__(64) k_slots_softmax_mask(const Board *__restrict__ boards, uint32_t first,
                                                            uint32_t n, const float *__restrict__ logits, float *out) {
     __shared__ float m[kPolicy];

@@ -179,8 +179,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_cleaf(TV T, BV B, const
 __global__ __launch_bounds__(64 * kWavesPerBlock) void k_cexpand(TV T, BV B, uint32_t max_n,
                                                                 const uint32_t *__restrict__ count, int eval_kind,
                                                                 uint32_t *err) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t s = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    __shared__ uint32_t skey[kWavesPerBlock][kMaxMoves];
+    __shared__ float sval[kWavesPerBlock][kMaxMoves];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t s = blockIdx.x * kWavesPerBlock + w;
     if (s >= min(*count, max_n)) return;
     const uint32_t t = B.tree[s];
     const size_t base = tbase(T, t);
@@ -205,12 +207,47 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_cexpand(TV T, BV B, uin
         for (int i = lane; i < kPolicy; i += 64) se += expf(lg[i] - mx);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
+        // The renormalising sum is mask_invalid_actions' (chess.rs:252-275): the
+        // ndarray fold over the masked 4672-vector, 8 accumulators over the index
+        // classes i % 8 in ascending i, combined (0+4)+(1+5)+(2+6)+(3+7), as
+        // masked_normalize (chess_rules.hip) does it.  The masked entries are zeros
+        // and add exactly, so only the legal ones are summed: they are ranked by
+        // (class, index) and laid out in that order, and lane c < 8 folds class c.
+        // The priors then equal spai_chess_predict's bit for bit.
+        uint32_t key[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int j = lane + 64 * k;
-            p[k] = j < n ? expf(lg[policy_index(side, mv[j])] - mx) / se : 0.0f;
-            msum += p[k];
+            const uint32_t idx = j < n ? (uint32_t)policy_index(side, mv[j]) : 0u;
+            p[k] = j < n ? expf(lg[idx] - mx) / se : 0.0f;
+            key[k] = ((idx & 7u) << 21) | (idx << 8) | (uint32_t)j;   // idx < 2^13, j < 2^8: distinct keys
+            if (j < n) skey[w][j] = key[k];
         }
+        __builtin_amdgcn_wave_barrier();
+        uint32_t rank[4] = {0u, 0u, 0u, 0u};
+        uint32_t below = 0;   // legal moves of a class < lane (lanes >= 8: all n)
+        for (int i = 0; i < n; ++i) {
+            const uint32_t ki = skey[w][i];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (64 * k < n) rank[k] += ki < key[k];
+            below += (ki >> 21) < (uint32_t)lane;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (lane + 64 * k < n) sval[w][rank[k]] = p[k];
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t end = __shfl_down(below, 1, 64);
+        float acc = 0.0f;
+        if (lane < 8)
+            for (uint32_t r = below; r < end; ++r) acc = acc + sval[w][r];
+        float part[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) part[c] = __shfl(acc, c, 64);
+        msum = msum + (part[0] + part[4]);
+        msum = msum + (part[1] + part[5]);
+        msum = msum + (part[2] + part[6]);
+        msum = msum + (part[3] + part[7]);
         v = B.value[s];
     } else {
         const uint64_t key = T.leaf_key[t];
@@ -221,9 +258,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_cexpand(TV T, BV B, uin
             msum += p[k];   // small integers: exact in any order
         }
         v = eval_kind == SPAI_EVAL_HASH ? hash_value(key) : 0.0f;
-    }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) msum += __shfl_xor(msum, o, 64);
+        for (int o = 32; o > 0; o >>= 1) msum += __shfl_xor(msum, o, 64);
+    }
     const uint32_t first = T.fill[t];
     if (first + (uint32_t)n > T.cap) {
         if (lane == 0) atomicOr(err, kErrCap);
@@ -762,6 +799,37 @@ int tree_children(spai_chess *e, uint32_t tree, uint16_t *moves, uint32_t *visit
     for (uint32_t k = 0; k < (uint32_t)kMaxMoves; ++k) {
         if (moves) moves[k] = k < nch ? Tr.h_moves[k] : 0;
         if (visits) visits[k] = k < nch ? Tr.h_visits[k] : 0;
+    }
+    return SPAI_OK;
+}
+
+int tree_child_stats(spai_chess *e, uint32_t tree, uint16_t *moves, uint32_t *visits, float *value_sums, float *priors,
+                     uint32_t *n) {
+    Trees &Tr = e->trees;
+    SPAI_CHECK(tree < Tr.n, SPAI_ERR_INVALID, "tree %u out of range (%u trees)", tree, Tr.n);
+    SPAI_HIP(hipStreamSynchronize(e->stream));
+    uint32_t r = 0, h = 0, f = 0;
+    SPAI_HIP(hipMemcpy(&r, Tr.root.p + tree, 4, hipMemcpyDeviceToHost));
+    SPAI_HIP(hipMemcpy(&h, Tr.half.p + tree, 4, hipMemcpyDeviceToHost));
+    const size_t base = (size_t)tree * 2 * Tr.cap + (size_t)h * Tr.cap;   // the active half (tbase)
+    uint4 rec;
+    SPAI_HIP(hipMemcpy(&rec, Tr.nodes.p + base + r, 16, hipMemcpyDeviceToHost));
+    const uint32_t nch = rec.w >> 16;
+    SPAI_CHECK(nch <= (uint32_t)kMaxMoves, SPAI_ERR_INVALID, "internal: root with %u children", nch);
+    std::vector<uint4> ch(nch);
+    if (nch) {
+        SPAI_HIP(hipMemcpy(&f, Tr.first.p + base + r, 4, hipMemcpyDeviceToHost));
+        SPAI_CHECK((uint64_t)f + nch <= Tr.cap, SPAI_ERR_INVALID, "internal: children [%u, %u) past the arena", f,
+                   f + nch);
+        SPAI_HIP(hipMemcpy(ch.data(), Tr.nodes.p + base + f, 16ull * nch, hipMemcpyDeviceToHost));
+    }
+    if (n) *n = nch;
+    for (uint32_t k = 0; k < (uint32_t)kMaxMoves; ++k) {
+        const uint4 c = k < nch ? ch[k] : make_uint4(0, 0, 0, 0);
+        if (moves) moves[k] = (uint16_t)(c.w & 0xFFFFu);
+        if (visits) visits[k] = c.x;
+        if (value_sums) memcpy(value_sums + k, &c.y, 4);
+        if (priors) memcpy(priors + k, &c.z, 4);
     }
     return SPAI_OK;
 }

@@ -55,6 +55,7 @@ SYMBOLS = [
     "spai_chess_learner_train_batch", "spai_chess_learner_train", "spai_chess_learner_params",
     "spai_chess_learner_grads", "spai_chess_learner_activation", "spai_chess_learner_last_batch",
     "spai_chess_match_config_default", "spai_chess_match_run", "spai_chess_tree_children",
+    "spai_chess_tree_child_stats",
     "spai_chess_match_set_one_stream",
     # tictactoe (spai_ttt.py)
     "spai_ttt_create", "spai_ttt_destroy", "spai_ttt_games_resize", "spai_ttt_games_write", "spai_ttt_games_read",

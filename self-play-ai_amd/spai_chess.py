@@ -95,6 +95,7 @@ def lib():
         L.spai_chess_match_run.argtypes = [vp, P(ChessMatchPlayer), P(ChessMatchPlayer), u32, u64,
                                            P(ChessMatchConfig), P(ChessMatchGame), vp, P(ChessMatchStats)]
         L.spai_chess_tree_children.argtypes = [vp, u32, vp, vp, P(u32)]
+        L.spai_chess_tree_child_stats.argtypes = [vp, u32, vp, vp, vp, vp, P(u32)]
         L.spai_chess_match_set_one_stream.argtypes = [vp, i32]
         L.spai_chess_learner_create.argtypes = [vp, i32, vp, C.c_size_t, P(spai.AdamConfig), P(vp)]
         L.spai_chess_learner_destroy.argtypes = [vp]
@@ -292,6 +293,19 @@ class ChessEngine:
         n = C.c_uint32()
         _check(lib().spai_chess_tree_children(self.h, tree, _p(mv), _p(vis), C.byref(n)))
         return mv[:n.value].copy(), vis[:n.value].copy()
+
+    def tree_child_stats(self, tree):
+        """root children of a tree in stored (MoveGen) order, each exactly as its node record
+        holds it: (moves uint16 [n], visits uint32 [n], value_sums float32 [n], priors float32 [n]);
+        n = 0 while the root is not expanded.  Read-only: no search, the tree is unchanged"""
+        mv = np.zeros(MAX_MOVES, np.uint16)
+        vis = np.zeros(MAX_MOVES, np.uint32)
+        w = np.zeros(MAX_MOVES, np.float32)
+        pr = np.zeros(MAX_MOVES, np.float32)
+        n = C.c_uint32()
+        _check(lib().spai_chess_tree_child_stats(self.h, tree, _p(mv), _p(vis), _p(w), _p(pr), C.byref(n)))
+        k = n.value
+        return mv[:k].copy(), vis[:k].copy(), w[:k].copy(), pr[:k].copy()
 
     def match(self, a, b, n_games, game_id_base=0, opening_plies=2, max_plies=512, seed=0, start=None,
               keep_moves=True):
