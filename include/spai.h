@@ -662,6 +662,30 @@ int spai_chess_learner_grads(spai_chess_learner *l, float *grads, size_t n_param
  * [B][64], 2*blocks+3 the first value linear [B][256] */
 int spai_chess_learner_activation(spai_chess_learner *l, int layer, float *out, size_t n);
 int spai_chess_learner_last_batch(spai_chess_learner *l, uint32_t *n);
+/* The compute type of the conv GEMMs: SPAI_DTYPE_F32 (the default: the exact fp32
+ * step above) or SPAI_DTYPE_BF16 (mixed precision); anything else is
+ * SPAI_ERR_INVALID.  In bf16 every operand of every conv GEMM (forward, data
+ * gradient, weight gradient; trunk and policy head) is rounded to bf16, nearest
+ * even; the products are summed in fp32 and stored as fp32.  Bias, BatchNorm, the
+ * residual add, ReLU, the losses, the value head, Adam, the master parameters and
+ * every activation and gradient in device memory stay fp32; bf16 keeps fp32's
+ * exponent, so there is no loss scaling.  Still deterministic to the bit.  May be
+ * called between steps: drains the stream; parameters, Adam moments and step
+ * count are kept. */
+int spai_chess_learner_set_compute(spai_chess_learner *l, int dtype /* spai_dtype */);
+int spai_chess_learner_get_compute(spai_chess_learner *l, int *dtype);
+/* The checker's window, in both compute types.  With capture on (off is the default
+ * and costs nothing; on changes no result) a step keeps copies of the gradients it
+ * otherwise overwrites, and spai_chess_learner_gradient returns, of the last step:
+ * layer 0 .. 2*blocks the gradient with respect to that trunk conv's pre-BN output
+ * [B][256][64]; 2*blocks+1 the ReLU-masked gradient of the first policy conv's
+ * output [B][256][64]; 2*blocks+2 the logits' gradient [B][4672].
+ * SPAI_ERR_INVALID: no step yet, the last step was not captured, wrong n.
+ * spai_chess_learner_logits returns the last step's logits [B][4672] (needs no
+ * capture; SPAI_ERR_INVALID: no step yet, wrong n). */
+int spai_chess_learner_set_capture(spai_chess_learner *l, int on);
+int spai_chess_learner_gradient(spai_chess_learner *l, int layer, float *out, size_t n);
+int spai_chess_learner_logits(spai_chess_learner *l, float *out, size_t n);
 
 /* ------------------------------------------------------------ chess match
  * play() (main.rs:54-135, whose commented-out lines are the chess variant) with

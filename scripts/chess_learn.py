@@ -8,8 +8,11 @@
             ratio (--no-cpu skips it).  FLOPs per step: the three GEMMs (forward,
             data gradient, weight gradient) of the 2 blocks + 1 trunk convs, each
             2 x 64 B x 256 x 2304 (the stem counted as a full conv, the heads not
-            at all): 1.19 TFLOP at 20 blocks, B = 128.
-  --learn   spai_chess.learn() at a small configuration: the loss per iteration.
+            at all): 1.19 TFLOP at 20 blocks, B = 128.  --compute bf16 measures the
+            mixed-precision step and also gives the fraction of the 2.5 PF bf16
+            MFMA peak.
+  --learn   spai_chess.learn() at a small configuration: the loss per iteration
+            (--compute f32|bf16: the train step's compute type).
 
 Both merge their result into --out (default profiles/chess_learner/record.json).
 """
@@ -28,6 +31,7 @@ for p in (os.path.join(REPO, "tests"), os.path.join(REPO, "oracle"), os.path.joi
     sys.path.insert(0, p)
 
 PEAK_F32_MFMA = 157.3e12
+PEAK_BF16_MFMA = 2.5e15
 
 
 def step_flops(blocks, B):
@@ -47,7 +51,7 @@ def bench(args):
     for blocks, B in configs:
         x, pi, z = batches[B]
         p0 = sc.init_params(blocks, 0)
-        L = sc.ChessLearner(eng, blocks, p0)
+        L = sc.ChessLearner(eng, blocks, p0, compute=args.compute)
         for _ in range(args.warmup):
             L.train_batch(x, pi, z)
         t0 = time.perf_counter()
@@ -59,8 +63,11 @@ def bench(args):
         fl = step_flops(blocks, B)
         r = dict(device_ms_per_step=dev * 1e3, device_samples_per_s=B / dev, step_gflop=fl / 1e9,
                  device_tflops=fl / dev / 1e12, fraction_of_f32_mfma_peak=fl / dev / PEAK_F32_MFMA)
-        line = (f"{blocks}x256 B={B}: device {dev * 1e3:.2f} ms/step, {B / dev:.0f} samples/s, "
+        line = (f"{blocks}x256 B={B}: device ({args.compute}) {dev * 1e3:.2f} ms/step, {B / dev:.0f} samples/s, "
                 f"{fl / dev / 1e12:.1f} TF = {fl / dev / PEAK_F32_MFMA:.3f} of the f32 MFMA peak")
+        if args.compute == "bf16":
+            r["fraction_of_bf16_mfma_peak"] = fl / dev / PEAK_BF16_MFMA
+            line += f", {fl / dev / PEAK_BF16_MFMA:.4f} of the bf16 MFMA peak"
         if not args.no_cpu:
             forward, T, _ = LR.torch_net(p0, blocks, torch.float32)
             opt = torch.optim.Adam([t for t, _ in T if t.requires_grad], lr=1e-3)
@@ -83,7 +90,10 @@ def bench(args):
         out[f"{blocks}x{B}"] = r
         print(line, flush=True)
     eng.close()
-    rec = dict(steps=args.steps, warmup=args.warmup, peak_f32_mfma_tflops=PEAK_F32_MFMA / 1e12, results=out)
+    rec = dict(steps=args.steps, warmup=args.warmup, compute=args.compute, peak_f32_mfma_tflops=PEAK_F32_MFMA / 1e12,
+               results=out)
+    if args.compute == "bf16":
+        rec["peak_bf16_mfma_tflops"] = PEAK_BF16_MFMA / 1e12
     if not args.no_cpu:
         rec.update(cpu_threads=args.cpu_threads, cpu_steps=args.cpu_steps, torch=torch.__version__)
     return rec
@@ -94,7 +104,7 @@ def learn(args):
     cfg = dict(num_learn_iters=args.iters, num_self_play_iters=args.self_play_iters,
                num_parallel_self_play_games=args.games, batch_size=args.batch, num_epochs=args.epochs,
                num_searches=args.sims, blocks=args.blocks, seed=args.seed, clone_self_play=not args.distinct,
-               window=args.window)
+               window=args.window, compute=args.compute)
     with tempfile.TemporaryDirectory() as d:
         t0 = time.perf_counter()
         rec = sc.learn(checkpoint_dir=d, **cfg)
@@ -115,6 +125,7 @@ def main():
     ap.add_argument("--commit", default=None, help="commit hash to record (default: git rev-parse HEAD)")
     ap.add_argument("--tag", default="", help="record under bench_<tag> / learn_<tag>")
     ap.add_argument("--configs", default="10x32,10x128,20x32,20x128", help="--bench: blocks x B, comma separated")
+    ap.add_argument("--compute", choices=("f32", "bf16"), default="f32", help="the train step's compute type")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-cpu", action="store_true", help="--bench: skip the PyTorch CPU step")

@@ -1,5 +1,6 @@
 // chess_learner.hip — the train step of the chess net on the device
-// (model/chess.rs:48-70 under model/mod.rs:128-141), in fp32, behind
+// (model/chess.rs:48-70 under model/mod.rs:128-141), in fp32 or with the conv
+// GEMMs' operands in bf16 (spai_chess_learner_set_compute), behind
 // spai_chess_learner_* in include/spai.h; and spai_chess_net_set_params, the
 // in-place weight refresh of a self-play net that Learner::learn needs.
 //
@@ -45,6 +46,36 @@
 // linear gradients: one thread per entry, samples in order; loss: per-sample
 // terms, summed on the host in order.
 //
+// bf16 compute (opt-in; DESIGN.md section 2.2 is the contract, 9.1.1 the design):
+// every operand of every conv GEMM is rounded to bf16 (nearest even), the products are summed in
+// fp32 on v_mfma_f32_32x32x16_bf16 and stored as fp32; everything else, and every
+// tensor in HBM, stays fp32.  A lane's fragment is 8 consecutive K, so the LDS
+// images are not the f32 kernels':
+//
+//  * k_cl_pack writes, at the start of each step, a bf16 shadow of every conv's
+//    weights laid out as the A fragments themselves ([32-channel tile][tap][16-K
+//    step][lane][8]), once as the forward reads them and once transposed with the
+//    taps flipped for the data gradient, zero past the layer's channels.  A wave
+//    loads its fragment straight from that shadow (16 B a lane, 1 KiB a wave,
+//    consecutive), one tap ahead of the MFMAs; the weights never enter LDS.
+//  * k_cl_conv_bf16<TAPS>, forward and data gradient (they differ only in the shadow
+//    they are given).  A workgroup (2 waves) owns one sample times 64 output
+//    channels; a wave owns 32 channels times all 64 cells (two accumulators), so a
+//    weight fragment serves two MFMAs.  Per chunk of 64 source channels the sample's
+//    fp32 planes are read, rounded and stored channel-innermost, [10 x 10 position]
+//    [64 channels + 8], so a B fragment (8 channels at one tap-shifted cell) is one
+//    aligned 16-byte read.
+//  * k_cl_wgrad_bf16<TAPS>, weight gradient: (chunk of kWgSamples samples, 64 x 64
+//    channels), 4 waves of 32 x 32, one accumulator per tap.  K runs over cells, a
+//    fragment is one board row.  dz is stored [channel][64 cells]; the input is
+//    stored three times, shifted by dx = -1, 0, +1 with the zero the shift brings in
+//    (the thread that loaded the row has all three in registers), under zero halo
+//    rows, so every tap's fragment is again one aligned 16-byte read.  The partials
+//    go through the same k_cl_wreduce.
+//
+// In bf16 an MFMA chain runs over the whole K in one fp32 accumulator (the operand
+// rounding, 2^-9 relative, is far above the chain's own noise); the order is fixed.
+//
 // This file holds what is chess's: the conv, weight-gradient and head kernels, the
 // step's launch chain and the entry points.  The BatchNorm and Adam kernels
 // (k_lc_bn_fwd<64>, k_lc_bn_bwd<64>, k_lc_adam), the workgroup reductions, the
@@ -68,6 +99,9 @@ using lc::Conv;
 using lc::kBnThreads;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kCells = 64, kHid = 256, kPolC = 73, kMaxBlocks = 40;
 constexpr int kEnc = kPlanes * kCells;   // 1216
@@ -264,6 +298,226 @@ __global__ void k_cl_wreduce(const float *__restrict__ part, int chunks, int CO,
     dw[i] = acc;
 }
 
+// ------------------------------------------------------------------ bf16 compute
+// two floats rounded to nearest even, packed (v_cvt_pk_bf16_f32)
+__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){a, b}, bf16x2));
+}
+__device__ __forceinline__ uint4 pack_bf16x8(const float *v) {
+    return make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]),
+                      pack_bf16x2(v[6], v[7]));
+}
+__device__ __forceinline__ f32x16 mfma_bf16(uint4 a, uint4 b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
+                                                   0, 0);
+}
+
+constexpr int kBfKC = 64;   // source channels per chunk of k_cl_conv_bf16 = 4 K steps of 16
+
+// the bf16 shadow of layer blockIdx.y's weights w [CO][CI][TAPS] as k_cl_conv_bf16's A
+// fragments: out[((mt TAPS + t) KS + ks) 64 + lane], lane = 32 h + r, holds
+// Wm[m = 32 mt + r][k = 16 ks + 8 h + j] at tap t in element j;
+// mode 0 (forward):       Wm[m][k] = w[m][k][t]
+// mode 1 (data gradient): Wm[m][k] = w[k][m][TAPS-1-t]
+// and zero past the layer's channels (MT 32-row tiles, KS 16-K steps are padded counts)
+__global__ void k_cl_pack(const float *__restrict__ w, size_t wstride, int CO, int CI, int TAPS, int mode,
+                          uint4 *__restrict__ out, size_t ostride, int MT, int KS) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= MT * TAPS * KS * 64) return;
+    w += blockIdx.y * wstride;
+    out += blockIdx.y * ostride;
+    const int lane = i & 63;
+    int q = i >> 6;
+    const int ks = q % KS;
+    q /= KS;
+    const int t = q % TAPS, mt = q / TAPS;
+    const int m = 32 * mt + (lane & 31), k0 = 16 * ks + 8 * (lane >> 5);
+    const int M = mode == 0 ? CO : CI, K = mode == 0 ? CI : CO;
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int k = k0 + j;
+        v[j] = (m < M && k < K) ? (mode == 0 ? w[((size_t)m * CI + k) * TAPS + t]
+                                             : w[((size_t)k * CI + m) * TAPS + TAPS - 1 - t])
+                                : 0.0f;
+    }
+    out[i] = pack_bf16x8(v);
+}
+
+// k_cl_conv's product for sample blockIdx.x and output channels 64 blockIdx.y ..+63 with
+// both operands rounded to bf16: out[s][n][cell] = sum_{c,t} bf(src[s][c][cell + d(t)]) Wm[n][c] at t,
+// Wm the k_cl_pack shadow of the layer (forward or data gradient), KS its K steps.
+// wave = 32 output channels x 64 cells.  out may alias addend.
+template <int TAPS>
+__global__ __launch_bounds__(128) void k_cl_conv_bf16(const float *__restrict__ src, int csrc,
+                                                      const uint4 *__restrict__ wpk, int KS,
+                                                      const float *__restrict__ bias, int relu, const float *addend,
+                                                      float *out, int N) {
+    constexpr int NPOS = TAPS == 9 ? 100 : 64, PQ = kBfKC / 8 + 1;   // a position's row: 8 + 1 (pad) 16-byte groups
+    __shared__ uint4 planes[NPOS * PQ];                               // [position][channel of the chunk] bf16
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = blockIdx.x, mt = blockIdx.y * 2 + wave;
+    const int li = lane & 31, hk = lane >> 5;
+    // staging: cell = lane, channel groups (8 channels) wave + 2 j
+    float pr[4][8];
+    auto load = [&](int k0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int c = k0 + 8 * (wave + 2 * j) + e;
+                pr[j][e] = c < csrc ? src[((size_t)s * csrc + c) * kCells + lane] : 0.0f;
+            }
+    };
+    const int spos = TAPS == 9 ? ((lane >> 3) + 1) * 10 + (lane & 7) + 1 : lane;
+    auto store = [&]() {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) planes[spos * PQ + wave + 2 * j] = pack_bf16x8(pr[j]);
+    };
+    if (TAPS == 9) {   // the halo: zero once, only the interior is ever stored
+        for (int i = tid; i < NPOS * PQ; i += 128) planes[i] = make_uint4(0, 0, 0, 0);
+        __syncthreads();
+    }
+    const uint4 *wa = wpk + (size_t)mt * TAPS * KS * 64 + lane;
+    uint4 an[4];
+    auto load_a = [&](int chunk, int t) {
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) an[kk] = wa[((size_t)t * KS + chunk * 4 + kk) * 64];
+    };
+    f32x16 acc[2];
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[rt][r] = 0.0f;
+    const int nchunks = KS / 4;
+    load(0);
+    load_a(0, 0);
+    for (int chunk = 0; chunk < nchunks; ++chunk) {
+        store();
+        __syncthreads();
+        if (chunk + 1 < nchunks) load((chunk + 1) * kBfKC);   // in flight under this chunk's MFMAs
+#pragma unroll
+        for (int t = 0; t < TAPS; ++t) {
+            uint4 a[4];
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) a[kk] = an[kk];
+            if (t + 1 < TAPS) load_a(chunk, t + 1);   // the next tap's weights, one tap ahead
+            else if (chunk + 1 < nchunks) load_a(chunk + 1, 0);
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt) {
+                const int cell = rt * 32 + li;
+                const int po = TAPS == 9 ? ((cell >> 3) + t / 3) * 10 + (cell & 7) + t % 3 : cell;
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) acc[rt] = mfma_bf16(a[kk], planes[po * PQ + 2 * kk + hk], acc[rt]);
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {   // D: column lane & 31, row (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+            const int n = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hk;
+            if (n < N) {
+                const size_t idx = ((size_t)s * N + n) * kCells + rt * 32 + li;
+                float v = acc[rt][r];
+                if (bias) v += bias[n];
+                if (addend) v += addend[idx];
+                if (relu) v = fmaxf(v, 0.0f);
+                out[idx] = v;
+            }
+        }
+}
+
+// k_cl_wgrad's partial with both operands rounded to bf16 (same grid, same partials):
+// part[chunk][t][co][ci] = sum_{s, cell} bf(dz[s][co][cell]) bf(in[s][ci][cell + d(t)])
+// 4 waves = 2 x 2 tiles of 32 x 32, an accumulator per tap; K = cells, a fragment = a board row
+template <int TAPS>
+__global__ __launch_bounds__(256) void k_cl_wgrad_bf16(const float *__restrict__ dz, int CO,
+                                                       const float *__restrict__ in, int CI,
+                                                       float *__restrict__ part, int B) {
+    constexpr int TW = TAPS == 9 ? 3 : 1;        // images of the input, one per x shift
+    constexpr int DQ = 9;                        // dz row: 8 board rows + 1 (pad) 16-byte groups
+    constexpr int IQ = TAPS == 9 ? 11 : 9;       // input row: (halo +) 8 board rows (+ halo) + 1 (pad)
+    __shared__ uint4 dzs[64 * DQ];
+    __shared__ uint4 ins[TW * 64 * IQ];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nci = (CI + 63) / 64;
+    const int cot = blockIdx.x / nci, cit = blockIdx.x - cot * nci, chunk = blockIdx.y;
+    const int co0 = cot * 64, ci0 = cit * 64;
+    const int s0 = chunk * kWgSamples, s1 = min(B, s0 + kWgSamples);
+    const int li = lane & 31, hk = lane >> 5, cm = wave & 1, cn = wave >> 1;
+    // staging: board row y = tid & 7 of channels (tid >> 3) + 32 j
+    const int sy = tid & 7, sc = tid >> 3;
+    float4 ra[2][2], rb[2][2];
+    auto load = [&](int s) {
+        const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int c = sc + 32 * j;
+            const float4 *pa = (const float4 *)(dz + ((size_t)s * CO + co0 + c) * kCells + 8 * sy);
+            const float4 *pb = (const float4 *)(in + ((size_t)s * CI + ci0 + c) * kCells + 8 * sy);
+            const bool oka = co0 + c < CO, okb = ci0 + c < CI;
+            ra[j][0] = oka ? pa[0] : zero;
+            ra[j][1] = oka ? pa[1] : zero;
+            rb[j][0] = okb ? pb[0] : zero;
+            rb[j][1] = okb ? pb[1] : zero;
+        }
+    };
+    auto store = [&]() {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int c = sc + 32 * j;
+            const float a[8] = {ra[j][0].x, ra[j][0].y, ra[j][0].z, ra[j][0].w,
+                                ra[j][1].x, ra[j][1].y, ra[j][1].z, ra[j][1].w};
+            dzs[c * DQ + sy] = pack_bf16x8(a);
+            const float b[10] = {0.0f,       rb[j][0].x, rb[j][0].y, rb[j][0].z, rb[j][0].w,
+                                 rb[j][1].x, rb[j][1].y, rb[j][1].z, rb[j][1].w, 0.0f};
+            if (TAPS == 9) {   // image tx holds in[y][x + tx - 1] at x, under halo row 0
+#pragma unroll
+                for (int tx = 0; tx < 3; ++tx) ins[(tx * 64 + c) * IQ + sy + 1] = pack_bf16x8(b + tx);
+            } else {
+                ins[c * IQ + sy] = pack_bf16x8(b + 1);
+            }
+        }
+    };
+    if (TAPS == 9) {   // the halo rows: zero once, only the board rows are ever stored
+        for (int i = tid; i < TW * 64 * IQ; i += 256) ins[i] = make_uint4(0, 0, 0, 0);
+        __syncthreads();
+    }
+    f32x16 acc[TAPS];
+#pragma unroll
+    for (int t = 0; t < TAPS; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+    load(s0);
+    for (int s = s0; s < s1; ++s) {
+        store();
+        __syncthreads();
+        if (s + 1 < s1) load(s + 1);
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const int y = 2 * ks + hk;                            // cells 8 y .. 8 y + 7
+            const uint4 a = dzs[(cm * 32 + li) * DQ + y];         // A[m = co][k = cell]
+#pragma unroll
+            for (int t = 0; t < TAPS; ++t) {
+                const int row = TAPS == 9 ? y + t / 3 : y;        // halo row index of board row y + dy
+                const uint4 b = ins[((TAPS == 9 ? t % 3 : 0) * 64 + cn * 32 + li) * IQ + row];   // B[k = cell][n = ci]
+                acc[t] = mfma_bf16(a, b, acc[t]);
+            }
+        }
+        __syncthreads();
+    }
+    const int ci = ci0 + cn * 32 + li;
+#pragma unroll
+    for (int t = 0; t < TAPS; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int co = co0 + cm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hk;
+            if (co < CO && ci < CI) part[(((size_t)chunk * TAPS + t) * CO + co) * CI + ci] = acc[t][r];
+        }
+}
+
 // a conv with bias and no BN, channel blockIdx.x: d becomes d [a > 0] (a: its ReLU
 // output, or NULL for none), g_bias[c] = its sum
 __global__ __launch_bounds__(kBnThreads) void k_cl_bias_grad(float *__restrict__ d, const float *__restrict__ a, int C,
@@ -424,6 +678,20 @@ struct Learner : lc::Core {   // batch_in: [x: B*1216 | pi: B*4672 | z: B]
     DevBuf<float> vc, h1, dh1, dvc;        // value head: [B][64], [B][256] and their gradients
     DevBuf<float> g0, g1, dz;              // backward: two activation-gradient buffers and dz, [B][256][64]
     DevBuf<float> wpart;                   // weight-gradient partials [chunks][9][256][256]
+    // bf16 compute: the k_cl_pack shadows of a conv's weights, forward and data gradient
+    struct Shadow {
+        size_t fwd = 0, bwd = 0;           // offsets into wsh (16-byte groups)
+        int mt_f = 0, ks_f = 0, mt_b = 0, ks_b = 0;   // padded 32-row tiles and 16-K steps of each
+    };
+    int compute = SPAI_DTYPE_F32;
+    DevBuf<uint4> wsh;                     // allocated by the first bf16 step
+    size_t wsh_groups = 0;
+    std::vector<Shadow> sconvs;            // per trunk conv (the stem has no data gradient)
+    Shadow sp1, sp2;
+    // the checker's window: copies of the gradients a step overwrites
+    int capture = 0;
+    uint32_t captured_batch = 0;           // the last step's batch if it was captured
+    std::vector<DevBuf<float>> cap;        // per trunk conv: dz; then the masked gradient of the first policy conv
 };
 
 }  // namespace chess
@@ -452,15 +720,65 @@ int alloc_batch(spai_chess_learner *L, uint32_t B) {
     SPAI_TRY(L->h1.alloc((size_t)B * kHid));
     SPAI_TRY(L->dh1.alloc((size_t)B * kHid));
     SPAI_TRY(L->wpart.alloc((size_t)((B + kWgSamples - 1) / kWgSamples) * 9 * kHid * kHid));
+    for (auto &d : L->cap) d.release();   // regrown by the next captured step
+    L->captured_batch = 0;
     L->max_batch = B;
     return SPAI_OK;
 }
 
+// the capture buffers, for batches up to max_batch
+int alloc_capture(spai_chess_learner *L) {
+    for (auto &d : L->cap)
+        if (!d.p) SPAI_TRY(d.alloc((size_t)L->max_batch * kHid * kCells));
+    return SPAI_OK;
+}
+
+// the bf16 weight shadows
+int alloc_shadow(spai_chess_learner *L) {
+    if (L->wsh.p) return SPAI_OK;
+    return L->wsh.alloc(L->wsh_groups);
+}
+
+void pack_launch(const float *w, size_t wstride, int co, int ci, int taps, int mode, uint4 *out, size_t ostride, int mt,
+                 int ks, int layers, hipStream_t st) {
+    const int n = mt * taps * ks * 64;
+    k_cl_pack<<<dim3((n + 255) / 256, layers), 256, 0, st>>>(w, wstride, co, ci, taps, mode, out, ostride, mt, ks);
+}
+
+// refresh every shadow from the parameters (the start of a bf16 step)
+void pack_weights(spai_chess_learner *L, hipStream_t st) {
+    const float *P = L->p.p;
+    uint4 *S = L->wsh.p;
+    const Learner::Shadow &s0 = L->sconvs[0];
+    pack_launch(P + L->convs[0].w, 0, kHid, kPlanes, 9, 0, S + s0.fwd, 0, s0.mt_f, s0.ks_f, 1, st);
+    const int nres = (int)L->convs.size() - 1;
+    if (nres > 0) {   // the residual convs lie a fixed stride apart, in the parameters and in the shadow
+        const Learner::Shadow &s1 = L->sconvs[1];
+        const size_t wstride = nres > 1 ? L->convs[2].w - L->convs[1].w : 0;
+        const size_t ostride = nres > 1 ? L->sconvs[2].fwd - s1.fwd : 0;
+        pack_launch(P + L->convs[1].w, wstride, kHid, kHid, 9, 0, S + s1.fwd, ostride, s1.mt_f, s1.ks_f, nres, st);
+        pack_launch(P + L->convs[1].w, wstride, kHid, kHid, 9, 1, S + s1.bwd, ostride, s1.mt_b, s1.ks_b, nres, st);
+    }
+    pack_launch(P + L->p1_w, 0, kHid, kHid, 1, 0, S + L->sp1.fwd, 0, L->sp1.mt_f, L->sp1.ks_f, 1, st);
+    pack_launch(P + L->p1_w, 0, kHid, kHid, 1, 1, S + L->sp1.bwd, 0, L->sp1.mt_b, L->sp1.ks_b, 1, st);
+    pack_launch(P + L->p2_w, 0, kPolC, kHid, 1, 0, S + L->sp2.fwd, 0, L->sp2.mt_f, L->sp2.ks_f, 1, st);
+    pack_launch(P + L->p2_w, 0, kPolC, kHid, 1, 1, S + L->sp2.bwd, 0, L->sp2.mt_b, L->sp2.ks_b, 1, st);
+}
+
 // out = conv(src) of a layer with weights w [co][ci][taps]: forward (mode 0: src has ci
 // channels, out co) or data gradient (mode 1: src has co channels, out ci)
-void conv_launch(int mode, int taps, const float *src, int csrc, const float *w, const float *bias, int relu,
-                 const float *addend, float *out, int N, int B, hipStream_t st) {
+// sh: the layer's bf16 shadow when the learner computes in bf16, else NULL
+void conv_launch(spai_chess_learner *L, const Learner::Shadow *sh, int mode, int taps, const float *src, int csrc,
+                 const float *w, const float *bias, int relu, const float *addend, float *out, int N, int B,
+                 hipStream_t st) {
     const dim3 grid(B, (N + 63) / 64);
+    if (sh) {
+        const uint4 *wpk = L->wsh.p + (mode == 0 ? sh->fwd : sh->bwd);
+        const int ks = mode == 0 ? sh->ks_f : sh->ks_b;
+        if (taps == 9) k_cl_conv_bf16<9><<<grid, 128, 0, st>>>(src, csrc, wpk, ks, bias, relu, addend, out, N);
+        else k_cl_conv_bf16<1><<<grid, 128, 0, st>>>(src, csrc, wpk, ks, bias, relu, addend, out, N);
+        return;
+    }
     if (taps == 9) {
         if (mode == 0) k_cl_conv<0, 9, kConvKC3><<<grid, 256, 0, st>>>(src, csrc, w, bias, relu, addend, out, N);
         else k_cl_conv<1, 9, kConvKC3><<<grid, 256, 0, st>>>(src, csrc, w, bias, relu, addend, out, N);
@@ -475,16 +793,24 @@ void wgrad_launch(spai_chess_learner *L, int taps, const float *dz, int co, cons
                   hipStream_t st) {
     const int chunks = (B + kWgSamples - 1) / kWgSamples;
     const dim3 grid(((co + 63) / 64) * ((ci + 63) / 64), chunks);
-    if (taps == 9) k_cl_wgrad<9><<<grid, 768, 0, st>>>(dz, co, in, ci, L->wpart.p, B);
+    if (L->compute == SPAI_DTYPE_BF16) {
+        if (taps == 9) k_cl_wgrad_bf16<9><<<grid, 256, 0, st>>>(dz, co, in, ci, L->wpart.p, B);
+        else k_cl_wgrad_bf16<1><<<grid, 256, 0, st>>>(dz, co, in, ci, L->wpart.p, B);
+    } else if (taps == 9) k_cl_wgrad<9><<<grid, 768, 0, st>>>(dz, co, in, ci, L->wpart.p, B);
     else k_cl_wgrad<1><<<grid, 256, 0, st>>>(dz, co, in, ci, L->wpart.p, B);
     const int n = co * ci * taps;
     k_cl_wreduce<<<(n + 255) / 256, 256, 0, st>>>(L->wpart.p, chunks, co, ci, taps, dw);
 }
 
+const Learner::Shadow *shadow(spai_chess_learner *L, const Learner::Shadow *sh) {
+    return L->compute == SPAI_DTYPE_BF16 ? sh : nullptr;
+}
+
 void conv_fwd(spai_chess_learner *L, int l, const float *in, const float *res, int B, hipStream_t st) {
     const Conv &c = L->convs[l];
     float *P = L->p.p, *stat = L->stat.p + (size_t)l * 2 * kHid;
-    conv_launch(0, 9, in, c.ci, P + c.w, P + c.b, 0, nullptr, L->z[l].p, c.co, B, st);
+    conv_launch(L, shadow(L, &L->sconvs[l]), 0, 9, in, c.ci, P + c.w, P + c.b, 0, nullptr, L->z[l].p, c.co, B,
+                st);
     lc::k_lc_bn_fwd<kCells><<<c.co, kBnThreads, 0, st>>>(L->z[l].p, c.co, B, P + c.g, P + c.be, P + c.mu, P + c.var,
                                                          res, L->a[l].p, stat, stat + kHid, L->cfg.bn_momentum,
                                                          L->cfg.bn_eps);
@@ -498,8 +824,12 @@ void conv_bwd(spai_chess_learner *L, int l, float *da, int keep_dy, const float 
     float *P = L->p.p, *G = L->g.p, *stat = L->stat.p + (size_t)l * 2 * kHid;
     lc::k_lc_bn_bwd<kCells><<<c.co, kBnThreads, 0, st>>>(da, L->a[l].p, L->z[l].p, c.co, B, stat, stat + kHid, P + c.g,
                                                          L->dz.p, G + c.g, G + c.be, G + c.b, keep_dy);
+    if (L->capture)
+        (void)hipMemcpyAsync(L->cap[l].p, L->dz.p, (size_t)B * kHid * kCells * 4, hipMemcpyDeviceToDevice, st);
     wgrad_launch(L, 9, L->dz.p, c.co, in, c.ci, G + c.w, B, st);
-    if (dx) conv_launch(1, 9, L->dz.p, c.co, P + c.w, nullptr, 0, addend, dx, c.ci, B, st);
+    if (dx)
+        conv_launch(L, shadow(L, &L->sconvs[l]), 1, 9, L->dz.p, c.co, P + c.w, nullptr, 0, addend, dx, c.ci, B,
+                    st);
 }
 
 // one train step on the batch already in batch_in
@@ -508,6 +838,8 @@ int enqueue_step(spai_chess_learner *L, int B) {
     float *P = L->p.p, *G = L->g.p;
     const float *x = L->batch_in.p, *pi = x + (size_t)B * kEnc, *zt = pi + (size_t)B * kPolicy;
     const int nb = L->blocks;
+    const Learner::Shadow *sp1 = shadow(L, &L->sp1), *sp2 = shadow(L, &L->sp2);
+    if (L->compute == SPAI_DTYPE_BF16) pack_weights(L, st);
     conv_fwd(L, 0, x, nullptr, B, st);
     for (int k = 0; k < nb; ++k) {
         conv_fwd(L, 1 + 2 * k, L->a[2 * k].p, nullptr, B, st);
@@ -515,8 +847,8 @@ int enqueue_step(spai_chess_learner *L, int B) {
     }
     const float *tower = L->a[2 * nb].p;
     // policy head: relu(conv1x1 + bias), conv1x1 + bias = the logits [B][73 * 64]
-    conv_launch(0, 1, tower, kHid, P + L->p1_w, P + L->p1_b, 1, nullptr, L->ap1.p, kHid, B, st);
-    conv_launch(0, 1, L->ap1.p, kHid, P + L->p2_w, P + L->p2_b, 0, nullptr, L->logits.p, kPolC, B, st);
+    conv_launch(L, sp1, 0, 1, tower, kHid, P + L->p1_w, P + L->p1_b, 1, nullptr, L->ap1.p, kHid, B, st);
+    conv_launch(L, sp2, 0, 1, L->ap1.p, kHid, P + L->p2_w, P + L->p2_b, 0, nullptr, L->logits.p, kPolC, B, st);
     k_cl_policy_loss<<<B, kBnThreads, 0, st>>>(L->logits.p, pi, B, L->dlogits.p, L->terms.p);
     // value head, forward and backward; cur starts as its share of the trunk output's gradient
     float *cur = L->g0.p, *oth = L->g1.p;
@@ -529,10 +861,12 @@ int enqueue_step(spai_chess_learner *L, int B) {
     // policy head backward; the trunk output's gradient becomes complete in cur
     k_cl_bias_grad<<<kPolC, kBnThreads, 0, st>>>(L->dlogits.p, nullptr, kPolC, B, G + L->p2_b);
     wgrad_launch(L, 1, L->dlogits.p, kPolC, L->ap1.p, kHid, G + L->p2_w, B, st);
-    conv_launch(1, 1, L->dlogits.p, kPolC, P + L->p2_w, nullptr, 0, nullptr, oth, kHid, B, st);
+    conv_launch(L, sp2, 1, 1, L->dlogits.p, kPolC, P + L->p2_w, nullptr, 0, nullptr, oth, kHid, B, st);
     k_cl_bias_grad<<<kHid, kBnThreads, 0, st>>>(oth, L->ap1.p, kHid, B, G + L->p1_b);
+    if (L->capture)
+        (void)hipMemcpyAsync(L->cap.back().p, oth, (size_t)B * kHid * kCells * 4, hipMemcpyDeviceToDevice, st);
     wgrad_launch(L, 1, oth, kHid, tower, kHid, G + L->p1_w, B, st);
-    conv_launch(1, 1, oth, kHid, P + L->p1_w, nullptr, 0, cur, cur, kHid, B, st);
+    conv_launch(L, sp1, 1, 1, oth, kHid, P + L->p1_w, nullptr, 0, cur, cur, kHid, B, st);
     for (int k = nb - 1; k >= 0; --k) {
         conv_bwd(L, 2 + 2 * k, cur, 1, L->a[1 + 2 * k].p, oth, nullptr, B, st);   // cur becomes dy, the skip's share
         conv_bwd(L, 1 + 2 * k, oth, 0, L->a[2 * k].p, cur, cur, B, st);
@@ -541,6 +875,7 @@ int enqueue_step(spai_chess_learner *L, int B) {
     lc::adam_step(*L);
     SPAI_HIP(hipGetLastError());
     L->last_batch = (uint32_t)B;
+    L->captured_batch = L->capture ? (uint32_t)B : 0;
     return SPAI_OK;
 }
 
@@ -548,6 +883,8 @@ int train_batch(spai_chess_learner *L, uint32_t B, const float *states, const fl
                 float *loss3) {
     SPAI_CHECK(B >= 1 && B <= (1u << 16), SPAI_ERR_INVALID, "train_batch: batch of %u samples", B);
     SPAI_TRY(alloc_batch(L, B));
+    if (L->capture) SPAI_TRY(alloc_capture(L));
+    if (L->compute == SPAI_DTYPE_BF16) SPAI_TRY(alloc_shadow(L));
     bool finite = true;
     SPAI_TRY(lc::train_batch(*L, B, states, policies, values, loss3, &finite,
                              [&](int b) { return enqueue_step(L, b); }));
@@ -559,6 +896,8 @@ int train_batch(spai_chess_learner *L, uint32_t B, const float *states, const fl
 void learner_free(spai_chess_learner *L) {
     for (auto &d : L->z) d.release();
     for (auto &d : L->a) d.release();
+    for (auto &d : L->cap) d.release();
+    L->wsh.release();
     for (auto *d : {&L->stat, &L->ap1, &L->logits, &L->dlogits, &L->vc, &L->h1, &L->dh1, &L->dvc, &L->g0, &L->g1,
                     &L->dz, &L->wpart})
         d->release();
@@ -584,6 +923,26 @@ int learner_init(spai_chess_learner *L, const float *params) {
     const size_t nl = L->convs.size();
     L->z.resize(nl);
     L->a.resize(nl);
+    L->cap.resize(nl + 1);
+    // the shadows: rows padded to the 64 a workgroup owns, K to whole chunks, zeros beyond the layer
+    auto shadow_of = [&](int co, int ci, int taps, bool bwd) {
+        auto up = [](int v, int m) { return (v + m - 1) / m * m; };
+        Learner::Shadow s;
+        s.mt_f = up(co, 64) / 32;
+        s.ks_f = up(ci, kBfKC) / 16;
+        s.fwd = L->wsh_groups;
+        L->wsh_groups += (size_t)s.mt_f * taps * s.ks_f * 64;
+        if (bwd) {
+            s.mt_b = up(ci, 64) / 32;
+            s.ks_b = up(co, kBfKC) / 16;
+            s.bwd = L->wsh_groups;
+            L->wsh_groups += (size_t)s.mt_b * taps * s.ks_b * 64;
+        }
+        return s;
+    };
+    for (size_t l = 0; l < nl; ++l) L->sconvs.push_back(shadow_of(kHid, L->convs[l].ci, 9, l > 0));
+    L->sp1 = shadow_of(kHid, kHid, 1, true);
+    L->sp2 = shadow_of(kPolC, kHid, 1, true);
     SPAI_TRY(L->stat.alloc(nl * 2 * kHid));
     return lc::core_init(*L, params);
 }
@@ -672,6 +1031,64 @@ int spai_chess_learner_activation(spai_chess_learner *L, int layer, float *out, 
     const size_t want = (size_t)L->last_batch * per;
     SPAI_CHECK(n == want, SPAI_ERR_INVALID, "expected %zu activations, got %zu", want, n);
     SPAI_HIP(hipMemcpyAsync(out, src, n * 4, hipMemcpyDeviceToHost, L->stream));
+    SPAI_HIP(hipStreamSynchronize(L->stream));
+    return SPAI_OK;
+}
+
+int spai_chess_learner_set_compute(spai_chess_learner *L, int dtype) {
+    SPAI_PTR(L);
+    SPAI_CHECK(dtype == SPAI_DTYPE_F32 || dtype == SPAI_DTYPE_BF16, SPAI_ERR_INVALID, "compute type %d", dtype);
+    SPAI_SET_DEVICE(L);
+    SPAI_HIP(hipStreamSynchronize(L->stream));
+    if (dtype == SPAI_DTYPE_BF16) SPAI_TRY(alloc_shadow(L));
+    L->compute = dtype;
+    return SPAI_OK;
+}
+
+int spai_chess_learner_get_compute(spai_chess_learner *L, int *dtype) {
+    SPAI_PTR(L);
+    SPAI_PTR(dtype);
+    *dtype = L->compute;
+    return SPAI_OK;
+}
+
+int spai_chess_learner_set_capture(spai_chess_learner *L, int on) {
+    SPAI_PTR(L);
+    SPAI_SET_DEVICE(L);
+    SPAI_HIP(hipStreamSynchronize(L->stream));
+    L->capture = on != 0;
+    if (!L->capture) {
+        for (auto &d : L->cap) d.release();
+        L->captured_batch = 0;
+    }
+    return SPAI_OK;
+}
+
+int spai_chess_learner_gradient(spai_chess_learner *L, int layer, float *out, size_t n) {
+    SPAI_PTR(L);
+    SPAI_PTR(out);
+    SPAI_SET_DEVICE(L);
+    const int nt = (int)L->convs.size();   // trunk layers 0 .. 2 blocks
+    SPAI_CHECK(layer >= 0 && layer < nt + 2, SPAI_ERR_INVALID, "layer %d of %d", layer, nt + 2);
+    SPAI_CHECK(L->last_batch > 0, SPAI_ERR_INVALID, "no train step yet");
+    SPAI_CHECK(L->capture && L->captured_batch == L->last_batch, SPAI_ERR_INVALID,
+               "the last train step was not captured");
+    const float *src = layer <= nt ? L->cap[layer].p : L->dlogits.p;
+    const size_t want = (size_t)L->last_batch * (layer <= nt ? (size_t)kHid * kCells : (size_t)kPolicy);
+    SPAI_CHECK(n == want, SPAI_ERR_INVALID, "expected %zu gradients, got %zu", want, n);
+    SPAI_HIP(hipMemcpyAsync(out, src, n * 4, hipMemcpyDeviceToHost, L->stream));
+    SPAI_HIP(hipStreamSynchronize(L->stream));
+    return SPAI_OK;
+}
+
+int spai_chess_learner_logits(spai_chess_learner *L, float *out, size_t n) {
+    SPAI_PTR(L);
+    SPAI_PTR(out);
+    SPAI_SET_DEVICE(L);
+    SPAI_CHECK(L->last_batch > 0, SPAI_ERR_INVALID, "no train step yet");
+    const size_t want = (size_t)L->last_batch * kPolicy;
+    SPAI_CHECK(n == want, SPAI_ERR_INVALID, "expected %zu logits, got %zu", want, n);
+    SPAI_HIP(hipMemcpyAsync(out, L->logits.p, n * 4, hipMemcpyDeviceToHost, L->stream));
     SPAI_HIP(hipStreamSynchronize(L->stream));
     return SPAI_OK;
 }

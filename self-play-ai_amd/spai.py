@@ -54,6 +54,8 @@ SYMBOLS = [
     "spai_chess_net_set_params", "spai_chess_learner_create", "spai_chess_learner_destroy",
     "spai_chess_learner_train_batch", "spai_chess_learner_train", "spai_chess_learner_params",
     "spai_chess_learner_grads", "spai_chess_learner_activation", "spai_chess_learner_last_batch",
+    "spai_chess_learner_set_compute", "spai_chess_learner_get_compute", "spai_chess_learner_set_capture",
+    "spai_chess_learner_gradient", "spai_chess_learner_logits",
     "spai_chess_match_config_default", "spai_chess_match_run", "spai_chess_tree_children",
     "spai_chess_tree_child_stats",
     "spai_chess_match_set_one_stream",

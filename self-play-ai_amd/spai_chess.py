@@ -105,6 +105,11 @@ def lib():
         L.spai_chess_learner_grads.argtypes = [vp, vp, C.c_size_t]
         L.spai_chess_learner_activation.argtypes = [vp, i32, vp, C.c_size_t]
         L.spai_chess_learner_last_batch.argtypes = [vp, P(u32)]
+        L.spai_chess_learner_set_compute.argtypes = [vp, i32]
+        L.spai_chess_learner_get_compute.argtypes = [vp, P(i32)]
+        L.spai_chess_learner_set_capture.argtypes = [vp, i32]
+        L.spai_chess_learner_gradient.argtypes = [vp, i32, vp, C.c_size_t]
+        L.spai_chess_learner_logits.argtypes = [vp, vp, C.c_size_t]
         _ready = True
     return L
 
@@ -426,10 +431,47 @@ class ChessNet:
 
 class ChessLearner(DeviceLearner):
     """Device train step of the chess net (model/chess.rs under
-    model/mod.rs:128-141) on the engine's device and stream, in exact fp32:
-    train-mode forward, policy NLL + value MSE, backward, one Adam step.
-    Mirrors spai_ttt.TTTLearner."""
+    model/mod.rs:128-141) on the engine's device and stream: train-mode forward,
+    policy NLL + value MSE, backward, one Adam step.  Mirrors spai_ttt.TTTLearner.
+    compute: "f32" (the default, exact fp32) or "bf16" (the conv GEMMs' operands
+    rounded to bf16, fp32 sums; everything else fp32: spai.h)."""
     LIB, PREFIX, ENC, POLICY = staticmethod(lib), "spai_chess_learner", ENC, POLICY
+    COMPUTE = {"f32": 1, "bf16": 0}   # spai_dtype
+
+    def __init__(self, engine, blocks, params, compute="f32", **adam):
+        super().__init__(engine, blocks, params, **adam)
+        if compute != "f32":
+            self.set_compute(compute)
+
+    def set_compute(self, compute):
+        """between steps: parameters, Adam moments and step count are kept"""
+        if compute not in self.COMPUTE:
+            raise ValueError(f"compute {compute!r}: 'f32' or 'bf16'")
+        self._call("set_compute", self.h, self.COMPUTE[compute])
+
+    def compute(self):
+        d = C.c_int32()
+        self._call("get_compute", self.h, C.byref(d))
+        return {v: k for k, v in self.COMPUTE.items()}[d.value]
+
+    def set_capture(self, on):
+        """keep the gradients a step otherwise overwrites (for gradient()); changes no result"""
+        self._call("set_capture", self.h, int(bool(on)))
+
+    def gradient(self, layer):
+        """of the last (captured) train step: layers 0 .. 2*blocks the gradient of that
+        trunk conv's pre-BN output, 2*blocks+1 the masked gradient of the first policy
+        conv, [B][256][8][8]; 2*blocks+2 the logits' gradient, [B][4672]"""
+        nt, B = 2 * self.blocks + 1, self.last_batch()
+        out = np.zeros((B, 256, 8, 8) if layer <= nt else (B, POLICY), np.float32)
+        self._call("gradient", self.h, layer, _p(out), out.size)
+        return out
+
+    def logits(self):
+        """the last train step's logits [B][4672]"""
+        out = np.zeros((self.last_batch(), POLICY), np.float32)
+        self._call("logits", self.h, _p(out), out.size)
+        return out
 
     def activation(self, layer):
         """the last train step's post-ReLU activations: layers 0 .. 2*blocks the trunk
@@ -444,7 +486,7 @@ class ChessLearner(DeviceLearner):
 
 def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_games=100, batch_size=32, num_epochs=4,
           num_searches=600, temperature=1.25, c=2.0, blocks=10, seed=0, checkpoint_dir=".", clone_self_play=True,
-          params=None, device=0, on_train_set=None, window=None, max_moves=None):
+          params=None, device=0, on_train_set=None, window=None, max_moves=None, compute="f32"):
     """Learner::learn (learner.rs:98-196) for chess, with mcts.rs:46-59's defaults:
     per iteration i, self-play with the current weights on one ChessEngine (the net
     refreshed in place), Model::train on the samples, checkpoint i.safetensors.
@@ -456,14 +498,17 @@ def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_ga
     ids (the sampling streams) are disjoint across batches and learn iterations.
     window: play each batch through that many tree slots (ChessEngine.self_play).
     on_train_set(i, states, policies, values, game_ids) sees every training set.
+    compute: the train step's compute type, "f32" or "bf16" (ChessLearner).
     Returns per-iteration records: samples, loss [total, policy, value] of the last
     step, games, checkpoint."""
     G = num_parallel_self_play_games
+    if compute not in ChessLearner.COMPUTE:
+        raise ValueError(f"compute {compute!r}: 'f32' or 'bf16'")
     return learn_loop(
         lambda: ChessEngine(num_searches=num_searches, max_trees=G if window is None else int(window),
                             eval_kind=EVAL_NET, device=device, c=c, temperature=temperature, seed=seed,
                             max_moves=max_moves),
-        lambda eng, P: ChessNet(eng, blocks, P), lambda eng, P: ChessLearner(eng, blocks, P),
+        lambda eng, P: ChessNet(eng, blocks, P), lambda eng, P: ChessLearner(eng, blocks, P, compute=compute),
         init_params(blocks, seed) if params is None else params, blocks, 256, GAME_CHESS, num_learn_iters,
         num_self_play_iters, G, batch_size, num_epochs, seed, checkpoint_dir, clone_self_play, on_train_set,
         self_play_kw=dict(window=window))
