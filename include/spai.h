@@ -171,6 +171,11 @@ int spai_tree_use_subtree(spai_engine *eng, uint32_t tree, uint32_t child_id);
 /* arena[node].state for the root or a root child; visits / value_sum of that node (may be NULL) */
 int spai_tree_node(spai_engine *eng, uint32_t tree, uint32_t node_id, spai_c4_state *state, uint32_t *visits,
                    float *value_sum);
+/* The root's child records, read-only, in legal-action order: node id, N, W (value_sum) and
+ * the prior P of child k < n_children (the arrays hold 7; the rest are id 0xFFFFFFFF and
+ * zeros).  n_children = 0 for a root not yet expanded.  Any output pointer may be NULL. */
+int spai_tree_child_stats(spai_engine *eng, uint32_t tree, uint32_t *child_ids, uint32_t *visits, float *value_sums,
+                          float *priors, uint32_t *n_children);
 int spai_tree_size(spai_engine *eng, uint32_t tree, uint32_t *nodes);
 
 /* ------------------------------------------------------------------ self-play

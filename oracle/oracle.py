@@ -234,8 +234,10 @@ class Net:
 
 
 # ---------------------------------------------------------------- search / self-play
-def search_c4(states, num_searches, eval_kind=EVAL_HASH, net=None, c=2.0, trees=None):
-    """Run Mcts::search over fresh trees rooted at `states` (or given tree handles)."""
+def search_c4(states, num_searches, eval_kind=EVAL_HASH, net=None, c=2.0, trees=None, eval_fn=None):
+    """Run Mcts::search over fresh trees rooted at `states` (or given tree handles).
+    eval_fn: a callable (user, n, states, priors, values) that evaluates the leaves
+    instead of eval_kind / net, as in self_play."""
     L = lib()
     own = trees is None
     if own:
@@ -246,7 +248,8 @@ def search_c4(states, num_searches, eval_kind=EVAL_HASH, net=None, c=2.0, trees=
     ids = np.zeros((n, 7), np.int32)
     vis = np.zeros((n, 7), np.float32)
     nc = np.zeros(n, np.int32)
-    rc = L.or_search(arr, n, num_searches, c, eval_kind, net.h if net else None, EVAL_FN(), None,
+    cb = EVAL_FN(eval_fn) if eval_fn is not None else EVAL_FN()
+    rc = L.or_search(arr, n, num_searches, c, eval_kind, net.h if net else None, cb, None,
                      _f(pol), _i(ids), _f(vis), _i(nc))
     if own:
         for t in trees:

@@ -350,6 +350,11 @@ int spai_tree_node(spai_engine *e, uint32_t t, uint32_t node, spai_c4_state *st,
     ENG_CHECK(e);
     return tree_node(e, t, node, st, visits, w);
 }
+int spai_tree_child_stats(spai_engine *e, uint32_t t, uint32_t *child_ids, uint32_t *visits, float *value_sums,
+                          float *priors, uint32_t *n_children) {
+    ENG_CHECK(e);
+    return tree_child_stats(e, t, child_ids, visits, value_sums, priors, n_children);
+}
 int spai_tree_size(spai_engine *e, uint32_t t, uint32_t *nodes) {
     ENG_CHECK(e);
     SPAI_PTR(nodes);

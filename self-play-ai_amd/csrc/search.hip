@@ -1144,6 +1144,38 @@ int tree_node(spai_engine *e, uint32_t t, uint32_t node, spai_c4_state *st, uint
     return SPAI_OK;
 }
 
+// The root's child records as they stand on the device: read-only, the root taken from the
+// device's own table (a move step re-roots there), bounds checked before the second read.
+int tree_child_stats(spai_engine *e, uint32_t t, uint32_t *child_ids, uint32_t *visits, float *value_sums,
+                     float *priors, uint32_t *n_children) {
+    Trees &T = e->trees;
+    SPAI_CHECK(t < T.n_trees, SPAI_ERR_INVALID, "tree %u out of range", t);
+    SPAI_HIP(hipStreamSynchronize(e->stream));
+    uint32_t r = 0;
+    SPAI_HIP(hipMemcpy(&r, T.root.p + t, 4, hipMemcpyDeviceToHost));
+    SPAI_CHECK(r < T.cap, SPAI_ERR_INVALID, "internal: root %u past the arena", r);
+    const uint4 *nodes = T.nodes.p + (size_t)t * T.cap;
+    uint4 rec;
+    SPAI_HIP(hipMemcpy(&rec, nodes + r, 16, hipMemcpyDeviceToHost));
+    const uint32_t nch = root_children(rec.w), first = rec.w & 0xFFFFFFu;
+    SPAI_CHECK(nch <= (uint32_t)c4::kActions, SPAI_ERR_INVALID, "internal: root with %u children", nch);
+    uint4 ch[c4::kActions];
+    if (nch) {
+        SPAI_CHECK((uint64_t)first + nch <= T.cap, SPAI_ERR_INVALID, "internal: children [%u, %u) past the arena",
+                   first, first + nch);
+        SPAI_HIP(hipMemcpy(ch, nodes + first, 16ull * nch, hipMemcpyDeviceToHost));
+    }
+    if (n_children) *n_children = nch;
+    for (uint32_t k = 0; k < (uint32_t)c4::kActions; ++k) {
+        const uint4 c = k < nch ? ch[k] : make_uint4(0, 0, 0, 0);
+        if (child_ids) child_ids[k] = k < nch ? first + k : kNoChildren;
+        if (visits) visits[k] = c.x;
+        if (value_sums) memcpy(value_sums + k, &c.y, 4);
+        if (priors) memcpy(priors + k, &c.z, 4);
+    }
+    return SPAI_OK;
+}
+
 int tree_size(spai_engine *e, uint32_t t, uint32_t *nodes) {
     Trees &T = e->trees;
     SPAI_CHECK(t < T.n_trees, SPAI_ERR_INVALID, "tree %u out of range", t);

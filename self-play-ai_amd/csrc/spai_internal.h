@@ -349,6 +349,8 @@ int search(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_se
            uint32_t *child_ids, float *child_visits, uint32_t *n_children, double *evals_out);
 int tree_use_subtree(spai_engine *e, uint32_t t, uint32_t child);
 int tree_node(spai_engine *e, uint32_t t, uint32_t node, spai_c4_state *st, uint32_t *visits, float *w);
+int tree_child_stats(spai_engine *e, uint32_t t, uint32_t *child_ids, uint32_t *visits, float *value_sums,
+                     float *priors, uint32_t *n_children);
 int tree_size(spai_engine *e, uint32_t t, uint32_t *nodes);
 // selfplay.hip
 int selfplay_run(spai_engine *e, uint32_t n_games, uint64_t gid_base, spai_sample_sink sink, void *user,

@@ -31,7 +31,7 @@ SYMBOLS = [
     "spai_games_read", "spai_legal_mask", "spai_apply", "spai_value_terminated", "spai_encode",
     "spai_mask_invalid", "spai_rules_bench", "spai_net_num_params", "spai_net_init_params", "spai_net_create",
     "spai_net_destroy", "spai_net_forward", "spai_predict", "spai_engine_set_net", "spai_trees_create",
-    "spai_tree_reset", "spai_search", "spai_tree_use_subtree", "spai_tree_node", "spai_tree_size",
+    "spai_tree_reset", "spai_search", "spai_tree_use_subtree", "spai_tree_node", "spai_tree_child_stats", "spai_tree_size",
     "spai_selfplay_run", "spai_selfplay_stream", "spai_eval_cache_set_capacity", "spai_eval_cache_get_stats",
     "spai_match_config_default", "spai_match_run",
     "spai_engine_set_timing", "spai_engine_timing", "spai_engine_timing_items",
@@ -194,6 +194,7 @@ def lib():
         L.spai_search.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp]
         L.spai_tree_use_subtree.argtypes = [vp, u32, u32]
         L.spai_tree_node.argtypes = [vp, u32, u32, vp, vp, vp]
+        L.spai_tree_child_stats.argtypes = [vp, u32, vp, vp, vp, vp, P(u32)]
         L.spai_tree_size.argtypes = [vp, u32, vp]
         L.spai_selfplay_run.argtypes = [vp, u32, u64, SINK, vp, P(SelfPlayStats)]
         L.spai_selfplay_stream.argtypes = [vp, u32, u32, u64, SINK, vp, P(SelfPlayStats)]
@@ -441,6 +442,18 @@ class Engine:
         w = C.c_float()
         _check(lib().spai_tree_node(self.h, t, int(node), _p(a), C.byref(vis), C.byref(w)))
         return a[0], vis.value, w.value
+
+    def tree_child_stats(self, t):
+        """the root's child records in legal-action order -> (child_ids uint32 [k], visits uint32 [k],
+        value_sums float32 [k], priors float32 [k]); k = 0 for a root not yet expanded"""
+        ids = np.zeros(7, np.uint32)
+        vis = np.zeros(7, np.uint32)
+        w = np.zeros(7, np.float32)
+        pr = np.zeros(7, np.float32)
+        n = C.c_uint32()
+        _check(lib().spai_tree_child_stats(self.h, int(t), _p(ids), _p(vis), _p(w), _p(pr), C.byref(n)))
+        k = n.value
+        return ids[:k].copy(), vis[:k].copy(), w[:k].copy(), pr[:k].copy()
 
     def tree_size(self, t):
         n = C.c_uint32()

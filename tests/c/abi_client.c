@@ -2,7 +2,9 @@
  * Rust/Go/JNI binding would be (no C++ or torch types cross the boundary).
  *   abi_client host    host-only entry points (version, Policy helpers, errors)
  *   abi_client gpu N   + one Connect4 search of N sims over 3 trees with the
- *                        hash evaluator; prints visit counts per tree
+ *                        hash evaluator; prints visit counts per tree, then the
+ *                        root's child records (spai_tree_child_stats) per tree and
+ *                        the answers for a tree out of range and one never searched
  *   abi_client net PARAMS NPARAMS BLOCKS BOARDS N
  *                      Model::predict (model/mod.rs:36-98) through spai_net_create
  *                      + spai_predict on N positions, fp32 and bf16 nets: PARAMS is
@@ -196,6 +198,20 @@ int main(int argc, char **argv) {
         for (uint32_t k = 0; k < nch[t]; ++k) printf(" %.0f", visits[t * 7 + k]);
         printf("\n");
     }
+    for (uint32_t t = 0; t < 3; ++t) {
+        uint32_t cid[7], cn[7], k = 99;
+        float cw[7], cp[7];
+        CHECK(spai_tree_child_stats(e, t, cid, cn, cw, cp, &k));
+        printf("stats %u children %u", t, k);
+        for (uint32_t j = 0; j < 7; ++j) printf(" %u:%u:%u:%a:%a", cid[j] == ids[t * 7 + j], cid[j], cn[j], cw[j], cp[j]);
+        printf("\n");
+    }
+    uint32_t k = 99;
+    CHECK(spai_tree_child_stats(e, 0, NULL, NULL, NULL, NULL, NULL));   /* every output may be NULL */
+    printf("stats_range_rc %d\n", spai_tree_child_stats(e, 3, NULL, NULL, NULL, NULL, &k));
+    CHECK(spai_tree_reset(e, 2, NULL));
+    CHECK(spai_tree_child_stats(e, 2, NULL, NULL, NULL, NULL, &k));
+    printf("stats_fresh %u\n", k);
     CHECK(spai_engine_destroy(e));
     return 0;
 }

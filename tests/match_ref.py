@@ -5,7 +5,9 @@ or_tree_node_info, or_c4_next_state and or_u01_f32.  One game at a time, one
 search call per move: play() of main.rs:54-135 with a second evaluator where the
 human sits.
 
-A player is (eval_kind, oracle.Net or None, num_searches).
+A player is (eval_kind, oracle.Net or None, num_searches); in the net's place a
+callable (user, n, states, priors, values) evaluates that player's leaves instead
+(oracle.search_c4's eval_fn), whatever the eval kind.
 """
 import ctypes as C
 
@@ -77,7 +79,9 @@ def play_game(game_id, players, opening_plies, seed, c=2.0, trace=None):
         while state.status == orc.ONGOING:
             p = (game_id ^ state.n) & 1          # A (0) moves at the plies of the id's parity
             kind, net, ns = players[p]
-            rc, _pol, ids, vis, nc = orc.search_c4(None, ns, eval_kind=kind, net=net, c=c, trees=[trees[p]])
+            fn = net if callable(net) else None
+            rc, _pol, ids, vis, nc = orc.search_c4(None, ns, eval_kind=kind, net=None if fn else net, c=c,
+                                                   trees=[trees[p]], eval_fn=fn)
             if rc < 0:
                 raise MatchNaN("NaN UCB")
             sims[p] += ns

@@ -36,6 +36,10 @@ def test_c_client_host_entry_points(client):
     assert "empty policy" in lines["empty_error"]
 
 
+def _hexf(s):
+    return np.float32(float.fromhex(s))
+
+
 @pytest.mark.gpu
 def test_c_client_search_matches_oracle(client, oracle):
     out = subprocess.run([client, "gpu", "64"], capture_output=True, text=True, timeout=120)
@@ -46,10 +50,23 @@ def test_c_client_search_matches_oracle(client, oracle):
         n = int(r[3])
         assert n == nc[t]
         assert [int(v) for v in r[5:5 + n]] == [int(v) for v in vis[t, :n]]
-
-
-def _hexf(s):
-    return np.float32(float.fromhex(s))
+    # spai_tree_child_stats from C: the ids and visit counts the search returned, W and P of the
+    # hash evaluator's tree finite with the priors summing to 1, zeros past the children; a tree
+    # out of range is an error, a tree reset since has no children
+    stats = [l.split() for l in out.stdout.splitlines() if l.startswith("stats ")]
+    assert len(stats) == 3
+    for t, r in enumerate(stats):
+        n = int(r[3])
+        assert n == nc[t]
+        rec = [f.split(":") for f in r[4:11]]
+        assert all(f[0] == "1" for f in rec[:n])
+        assert [int(f[2]) for f in rec[:n]] == [int(v) for v in vis[t, :n]]
+        w = np.array([_hexf(f[3]) for f in rec[:n]])
+        p = np.array([_hexf(f[4]) for f in rec[:n]])
+        assert np.isfinite(w).all() and (p > 0).all() and abs(float(p.sum()) - 1.0) < 1e-5
+        assert all(f[1:] == [str(0xFFFFFFFF), "0", "0x0p+0", "0x0p+0"] for f in rec[n:])
+    lines = dict(l.split(" ", 1) for l in out.stdout.splitlines() if l.startswith("stats_"))
+    assert int(lines["stats_range_rc"]) == -1 and int(lines["stats_fresh"]) == 0
 
 
 @pytest.mark.gpu

@@ -64,3 +64,5 @@ def test_null_arguments_rejected(spai):
     assert spai.lib().spai_engine_create(1, None, 0, None) == -1
     assert b"NULL" in spai.lib().spai_last_error()
     assert spai.lib().spai_search(None, 0, None, 0, None, None, None, None) == -1
+    assert spai.lib().spai_tree_child_stats(None, 0, None, None, None, None, None) == -1
+    assert b"null engine" in spai.lib().spai_last_error()
