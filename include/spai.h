@@ -341,12 +341,22 @@ int spai_net_bench_conc(spai_net *net, uint32_t count, uint32_t iters, int conc,
  * without SyncBN) and the running statistics are averaged, so the replicas
  * stay identical. */
 typedef struct spai_learner spai_learner;
+/* The optimizer and train-mode BatchNorm settings of a learner (all three games).
+ * spai_*_learner_create checks the ranges below, returns SPAI_ERR_INVALID with a
+ * message that names the field, and leaves *out NULL; a NaN is out of every range.
+ *   eps > 0 is required, not merely advised: the BatchNorm running statistics
+ *   live in the parameter vector with gradient and moments 0, and they stay
+ *   where the forward put them only because 0 / (0 + eps) is 0 (eps = 0: NaN).
+ *   bn_eps and bn_momentum govern the train step alone.  The nets fold BatchNorm
+ *   into their conv weights with a fixed 1e-5 (spai_net_create,
+ *   spai_ttt_net_create / _set_params, spai_chess_net_create / _set_params), so
+ *   parameters trained with another bn_eps are evaluated with 1e-5 in self-play. */
 typedef struct spai_adam_config {
-    float lr;            /* 1e-3 */
-    float beta1, beta2;  /* 0.9, 0.999 */
-    float eps;           /* 1e-8 */
-    float bn_momentum;   /* 0.1 */
-    float bn_eps;        /* 1e-5 */
+    float lr;            /* 1e-3;  finite, >= 0 (0: only the running statistics move) */
+    float beta1, beta2;  /* 0.9, 0.999;  each in [0, 1) */
+    float eps;           /* 1e-8;  finite, > 0 */
+    float bn_momentum;   /* 0.1;  in [0, 1] */
+    float bn_eps;        /* 1e-5;  finite, > 0 */
 } spai_adam_config;
 #define SPAI_COMM_ID_BYTES 128
 

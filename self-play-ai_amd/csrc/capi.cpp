@@ -488,6 +488,7 @@ int spai_learner_create(spai_engine *e, int blocks, int hidden, const float *par
     ENG_CHECK(e);
     SPAI_PTR(params);
     SPAI_PTR(out);
+    *out = nullptr;
     return learner_create(e, blocks, hidden, params, n, cfg, out);
 }
 

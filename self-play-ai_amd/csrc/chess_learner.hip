@@ -956,15 +956,16 @@ int spai_chess_learner_create(spai_chess *e, int blocks, const float *params, si
     SPAI_PTR(e);
     SPAI_PTR(params);
     SPAI_PTR(out);
+    *out = nullptr;
     SPAI_CHECK(blocks >= 0 && blocks <= kMaxBlocks, SPAI_ERR_UNSUPPORTED, "chess learner: 0..%d blocks", kMaxBlocks);
     SPAI_CHECK(n_params == net_num_params(blocks), SPAI_ERR_INVALID, "expected %zu params, got %zu",
                net_num_params(blocks), n_params);
     SPAI_SET_DEVICE(e);
     spai_chess_learner *L = new (std::nothrow) spai_chess_learner();
     SPAI_CHECK(L, SPAI_ERR_INVALID, "out of host memory");
-    lc::core_setup(*L, e->device, e->stream, n_params, cfg, kEnc, kPolicy);
+    int rc = lc::core_setup(*L, e->device, e->stream, n_params, cfg, kEnc, kPolicy);
     L->blocks = blocks;
-    const int rc = learner_init(L, params);
+    if (rc == SPAI_OK) rc = learner_init(L, params);
     if (rc != SPAI_OK) {
         learner_free(L);
         return rc;

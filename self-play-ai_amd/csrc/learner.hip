@@ -1333,6 +1333,7 @@ int learner_create(spai_engine *e, int blocks, int hidden, const float *params, 
     SPAI_CHECK(blocks >= 0 && blocks <= 40, SPAI_ERR_UNSUPPORTED, "learner: 0..40 blocks (got %d)", blocks);
     SPAI_CHECK(params && n == net_num_params(e->game, blocks, hidden), SPAI_ERR_INVALID, "expected %zu params, got %zu",
                net_num_params(e->game, blocks, hidden), n);
+    SPAI_TRY(validate_adam_config(cfg));
     spai_learner *L = new spai_learner();
     L->eng = e;
     L->blocks = blocks;

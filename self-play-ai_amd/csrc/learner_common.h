@@ -19,6 +19,29 @@
 #include "spai_internal.h"
 
 namespace spai {
+
+// the ranges of spai_adam_config (include/spai.h), checked by every learner's create
+// (cfg NULL: the defaults).  Each comparison is false for a NaN, so a NaN is rejected
+// by the range it is held to.  eps > 0: the BN running statistics have g = m = v = 0
+// and stay put only because 0 / (0 + eps) is 0.
+inline int validate_adam_config(const spai_adam_config *cfg) {
+    if (!cfg) return SPAI_OK;
+    const auto finite_pos = [](float x) { return x > 0.0f && std::isfinite(x); };
+    SPAI_CHECK(cfg->lr >= 0.0f && std::isfinite(cfg->lr), SPAI_ERR_INVALID,
+               "adam config: lr must be finite and >= 0 (got %g)", (double)cfg->lr);
+    SPAI_CHECK(cfg->beta1 >= 0.0f && cfg->beta1 < 1.0f, SPAI_ERR_INVALID,
+               "adam config: beta1 must be in [0, 1) (got %g)", (double)cfg->beta1);
+    SPAI_CHECK(cfg->beta2 >= 0.0f && cfg->beta2 < 1.0f, SPAI_ERR_INVALID,
+               "adam config: beta2 must be in [0, 1) (got %g)", (double)cfg->beta2);
+    SPAI_CHECK(finite_pos(cfg->eps), SPAI_ERR_INVALID, "adam config: eps must be finite and > 0 (got %g)",
+               (double)cfg->eps);
+    SPAI_CHECK(cfg->bn_momentum >= 0.0f && cfg->bn_momentum <= 1.0f, SPAI_ERR_INVALID,
+               "adam config: bn_momentum must be in [0, 1] (got %g)", (double)cfg->bn_momentum);
+    SPAI_CHECK(finite_pos(cfg->bn_eps), SPAI_ERR_INVALID, "adam config: bn_eps must be finite and > 0 (got %g)",
+               (double)cfg->bn_eps);
+    return SPAI_OK;
+}
+
 namespace lc {
 
 // the fixed-order host sums of one step's loss terms [B][2] into loss3 = {total,
@@ -120,9 +143,10 @@ struct Core {
 };
 
 // a new learner's fields: the engine's device and stream, the Adam config (NULL:
-// defaults), the row widths
-inline void core_setup(Core &c, int device, hipStream_t stream, size_t n_params, const spai_adam_config *cfg,
-                       size_t xw, size_t pw) {
+// defaults; out of range: SPAI_ERR_INVALID), the row widths
+inline int core_setup(Core &c, int device, hipStream_t stream, size_t n_params, const spai_adam_config *cfg,
+                      size_t xw, size_t pw) {
+    SPAI_TRY(validate_adam_config(cfg));
     c.device = device;
     c.stream = stream;
     c.n_params = n_params;
@@ -130,6 +154,7 @@ inline void core_setup(Core &c, int device, hipStream_t stream, size_t n_params,
     else (void)spai_adam_config_default(&c.cfg);
     c.xw = xw;
     c.pw = pw;
+    return SPAI_OK;
 }
 
 // allocate and upload the parameters, zero the gradients and the moments

@@ -367,8 +367,9 @@ def check_learner_params(P, P_ref, g_refs, blocks, steps, lr=1e-3, tol=2e-5, run
     assert np.abs(P - P_ref).max() <= 2 * lr * steps + 1e-5                          # Adam step bound
 
 
-def torch_net(params, blocks, dtype=None):
-    """the net in PyTorch on the CPU from the flat parameters (train mode); returns
+def torch_net(params, blocks, dtype=None, momentum=0.1, bn_eps=1e-5):
+    """the net in PyTorch on the CPU from the flat parameters (train mode; BatchNorm's
+    momentum and eps as given); returns
     (forward(x) -> logits, value; the parameter tensors in flat order incl. running stats)"""
     import torch
     import torch.nn.functional as F
@@ -396,7 +397,7 @@ def torch_net(params, blocks, dtype=None):
 
     def cba(l, x, res=None):
         q = L[l]
-        y = F.batch_norm(F.conv2d(x, q["w"], q["b"], padding=1), q["mu"], q["var"], q["g"], q["be"], True, 0.1, 1e-5)
+        y = F.batch_norm(F.conv2d(x, q["w"], q["b"], padding=1), q["mu"], q["var"], q["g"], q["be"], True, momentum, bn_eps)
         return F.relu(y if res is None else y + res)
 
     def forward(x):
@@ -411,13 +412,14 @@ def torch_net(params, blocks, dtype=None):
     return forward, T, n
 
 
-def torch_train(params, batches, blocks, lr=1e-3, dtype=None):
-    """PyTorch CPU autograd (float64 by default): the same steps (torch.optim.Adam
-    defaults); returns per step (loss[3], grads, params) as float64 arrays"""
+def torch_train(params, batches, blocks, lr=1e-3, dtype=None, b1=0.9, b2=0.999, eps=1e-8, momentum=0.1, bn_eps=1e-5):
+    """PyTorch CPU autograd (float64 by default): the same steps (torch.optim.Adam and
+    BatchNorm at the given settings, the defaults being torch's); returns per step
+    (loss[3], grads, params) as float64 arrays"""
     import torch
     dtype = dtype or torch.float64
-    forward, T, n = torch_net(params, blocks, dtype)
-    opt = torch.optim.Adam([t for t, _ in T if t.requires_grad], lr=lr)
+    forward, T, n = torch_net(params, blocks, dtype, momentum, bn_eps)
+    opt = torch.optim.Adam([t for t, _ in T if t.requires_grad], lr=lr, betas=(b1, b2), eps=eps)
     out = []
 
     def flat(get):
@@ -443,15 +445,16 @@ def torch_train(params, batches, blocks, lr=1e-3, dtype=None):
     return out
 
 
-def torch_fp32_distance(p0, batches, blocks):
-    """how far PyTorch CPU fp32 lies from this restatement on the same steps: (loss,
+def torch_fp32_distance(p0, batches, blocks, **kw):
+    """how far PyTorch CPU fp32 lies from this restatement on the same steps at the
+    settings kw (train's keywords; none: the defaults): (loss,
     relative, worst step; gradient / max|g| at step 1, the step whose gradient the GPU
     test checks; well-conditioned parameters, absolute, last step; running statistics,
     absolute, last step) — the measurement behind the bars of
     tests/test_chess_learner_gpu.py"""
     import torch
-    P_ref, ref_losses, ref_grads = train(p0, batches, blocks)
-    got = torch_train(p0, batches, blocks, dtype=torch.float32)
+    P_ref, ref_losses, ref_grads = train(p0, batches, blocks, **kw)
+    got = torch_train(p0, batches, blocks, dtype=torch.float32, **kw)
     el = max(np.abs(g[0] - r).max() / np.abs(r).max() for g, r in zip(got, ref_losses))
     eg = np.abs(got[0][1] - ref_grads[0]).max() / np.abs(ref_grads[0]).max()
     well, running = learner_masks(blocks, ref_grads)

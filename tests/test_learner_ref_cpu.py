@@ -38,7 +38,7 @@ def c4_params(oracle, blocks, start):
 
 
 # ------------------------------------------------------------------ PyTorch autograd
-def torch_forward_backward(params, x, pi, z, blocks, dims, dtype):
+def torch_forward_backward(params, x, pi, z, blocks, dims, dtype, momentum=0.1, bn_eps=1e-5):
     """the model of gen_golden.learner_golden from a flat parameter vector, without the
     optimizer: train-mode forward, -(log_softmax(p) * pi).sum() / B + mse(v, z),
     backward.  Returns (parameters with the running statistics updated, gradients,
@@ -61,7 +61,7 @@ def torch_forward_backward(params, x, pi, z, blocks, dims, dtype):
     def cbn(t, name, res=None):
         t = F.conv2d(t, T[name + ".w"], T[name + ".b"], padding=1)
         t = F.batch_norm(t, T[name + ".mu"], T[name + ".var"], T[name + ".g"], T[name + ".be"], training=True,
-                         momentum=0.1, eps=1e-5)
+                         momentum=momentum, eps=bn_eps)
         return F.relu(t if res is None else t + res)
 
     B = len(x)

@@ -11,6 +11,8 @@ Shapes (n, batch, epochs), the smallest at which the loop can go wrong:
   (5, 2, 2)  three steps per epoch, the last of one sample (the smallest BatchNorm
              population), and a second pass over the same permutation
   (5, 8, 1)  batch > n: the loop clamps its host buffers to n, one step of 5
+Each at the default settings and at adam_ref.CONFIG_B, where every field of
+spai_adam_config is off its default (the default cases keep their test ids).
 """
 import numpy as np
 import pytest
@@ -43,27 +45,29 @@ def sc():
 _INPUTS = {}   # game -> (x, pi, z) of N samples, made once and never written
 
 
-def _open(game, spai, st, sc):
+def _open(game, spai, st, sc, adam=None):
     """the game's engine, its N samples, blocks = 1 parameters, a learner constructor
-    and how to read a learner's last batch size"""
+    (adam: its spai_adam_config fields, default none) and how to read a learner's last
+    batch size"""
+    adam = adam or {}
     if game == "connect4":
         from test_learner_shapes_gpu import _batches
         eng = spai.Engine(num_searches=1, max_trees=1)
         make = lambda: _batches(spai, eng, [N], seed=SEED)[0]   # noqa: E731
         p0 = spai.init_params(1, 64, seed=SEED)
-        new, last = (lambda: spai.Learner(eng, 1, p0)), (lambda L: L.last_batch)
+        new, last = (lambda: spai.Learner(eng, 1, p0, **adam)), (lambda L: L.last_batch)
     elif game == "tictactoe":
         from test_ttt_learner_gpu import _device_batches
         eng = st.TTTEngine(num_searches=1, max_trees=1)
         make = lambda: _device_batches(eng, N, 1, SEED)[0]   # noqa: E731
         p0 = st.init_params(1, SEED)
-        new, last = (lambda: st.TTTLearner(eng, 1, p0)), (lambda L: L.last_batch())
+        new, last = (lambda: st.TTTLearner(eng, 1, p0, **adam)), (lambda L: L.last_batch())
     else:
         from test_chess_learner_gpu import _device_batches, _engine
         eng = _engine(sc)
         make = lambda: _device_batches(sc, eng, N, 1, SEED)[0]   # noqa: E731
         p0 = sc.init_params(1, SEED)
-        new, last = (lambda: sc.ChessLearner(eng, 1, p0)), (lambda L: L.last_batch())
+        new, last = (lambda: sc.ChessLearner(eng, 1, p0, **adam)), (lambda L: L.last_batch())
     if game not in _INPUTS:
         _INPUTS[game] = tuple(np.ascontiguousarray(a) for a in make())
         for a in _INPUTS[game]:
@@ -71,10 +75,8 @@ def _open(game, spai, st, sc):
     return eng, _INPUTS[game], new, last
 
 
-@pytest.mark.parametrize("n,batch,epochs", SHAPES)
-@pytest.mark.parametrize("game", ["connect4", "tictactoe", "chess"])
-def test_train_is_its_train_batches(spai, st, sc, game, n, batch, epochs):
-    eng, (x, pi, z), new, last = _open(game, spai, st, sc)
+def _check_train_is_its_train_batches(spai, st, sc, game, n, batch, epochs, adam):
+    eng, (x, pi, z), new, last = _open(game, spai, st, sc, adam)
     assert len(z) == n
     A = new()
     loss_a = A.train(x, pi, z, epochs=epochs, batch=batch, seed=SEED)
@@ -94,3 +96,16 @@ def test_train_is_its_train_batches(spai, st, sc, game, n, batch, epochs):
     A.close()
     B.close()
     eng.close()
+
+
+@pytest.mark.parametrize("n,batch,epochs", SHAPES)
+@pytest.mark.parametrize("game", ["connect4", "tictactoe", "chess"])
+def test_train_is_its_train_batches(spai, st, sc, game, n, batch, epochs):
+    _check_train_is_its_train_batches(spai, st, sc, game, n, batch, epochs, None)
+
+
+@pytest.mark.parametrize("n,batch,epochs", SHAPES)
+@pytest.mark.parametrize("game", ["connect4", "tictactoe", "chess"])
+def test_train_is_its_train_batches_at_config_b(spai, st, sc, game, n, batch, epochs):
+    from adam_ref import CONFIG_B
+    _check_train_is_its_train_batches(spai, st, sc, game, n, batch, epochs, CONFIG_B)

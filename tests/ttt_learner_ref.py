@@ -284,9 +284,10 @@ def check_learner_params(P, P_ref, g_refs, blocks, steps, lr=1e-3, tol=2e-5):
     assert np.abs(P - P_ref).max() <= 2 * lr * steps + 1e-5                          # Adam step bound
 
 
-def torch_net(params, blocks):
-    """the net in PyTorch CPU fp32 from the flat parameters (train mode); returns
-    (forward(x) -> logits, value; the parameter tensors in flat order incl. running stats)"""
+def torch_net(params, blocks, momentum=0.1, bn_eps=1e-5):
+    """the net in PyTorch CPU fp32 from the flat parameters (train mode; BatchNorm's
+    momentum and eps as given); returns (forward(x) -> logits, value; the parameter
+    tensors in flat order incl. running stats)"""
     import torch
     import torch.nn.functional as F
     convs, lin, n = _layout(blocks)
@@ -308,7 +309,7 @@ def torch_net(params, blocks):
 
     def cba(l, x, res=None):
         q = L[l]
-        y = F.batch_norm(F.conv2d(x, q["w"], q["b"], padding=1), q["mu"], q["var"], q["g"], q["be"], True, 0.1, 1e-5)
+        y = F.batch_norm(F.conv2d(x, q["w"], q["b"], padding=1), q["mu"], q["var"], q["g"], q["be"], True, momentum, bn_eps)
         return F.relu(y if res is None else y + res)
 
     def forward(x):
@@ -322,12 +323,13 @@ def torch_net(params, blocks):
     return forward, T, n
 
 
-def torch_train(params, batches, blocks, lr=1e-3):
-    """PyTorch CPU fp32: the same steps (torch.optim.Adam defaults); returns per step
-    (loss[3], grads, params) as float32 arrays"""
+def torch_train(params, batches, blocks, lr=1e-3, b1=0.9, b2=0.999, eps=1e-8, momentum=0.1, bn_eps=1e-5):
+    """PyTorch CPU fp32: the same steps (torch.optim.Adam and BatchNorm at the given
+    settings, the defaults being torch's); returns per step (loss[3], grads, params) as
+    float32 arrays"""
     import torch
-    forward, T, n = torch_net(params, blocks)
-    opt = torch.optim.Adam([t for t, _ in T if t.requires_grad], lr=lr)
+    forward, T, n = torch_net(params, blocks, momentum, bn_eps)
+    opt = torch.optim.Adam([t for t, _ in T if t.requires_grad], lr=lr, betas=(b1, b2), eps=eps)
     out = []
 
     def flat(get):
@@ -350,3 +352,17 @@ def torch_train(params, batches, blocks, lr=1e-3):
         opt.step()
         out.append((np.array([(lp + lv).item(), lp.item(), lv.item()], np.float32), g, flat(lambda t: t)))
     return out
+
+
+def torch_fp32_distance(p0, batches, blocks, **kw):
+    """chess_learner_ref.torch_fp32_distance for this net: how far PyTorch CPU fp32 lies
+    from the restatement on the same steps at the settings kw (train's keywords): (loss,
+    relative, worst step; gradient / max|g| at step 1; well-conditioned parameters,
+    absolute, last step; running statistics, absolute, last step)"""
+    P_ref, ref_losses, ref_grads = train(p0, batches, blocks, **kw)
+    got = torch_train(p0, batches, blocks, **kw)
+    el = max(np.abs(g[0] - r).max() / np.abs(r).max() for g, r in zip(got, ref_losses))
+    eg = np.abs(got[0][1] - ref_grads[0]).max() / np.abs(ref_grads[0]).max()
+    well, running = learner_masks(blocks, ref_grads)
+    P = got[-1][2]
+    return el, eg, np.abs(P[well] - P_ref[well]).max(), np.abs(P[running] - P_ref[running]).max()
