@@ -96,7 +96,9 @@ constexpr int kPlanes = kBias + kBiasFloats * 4;   // stem neighbour planes [8][
                                                    // in different 16-B bank groups)
 constexpr int kPlaneRow = 34;
 constexpr int kWStem = kPlanes + kS * kPlaneRow * 8;   // stem weight fragments [4 ct][64 lanes] x 16 B, staged once
-constexpr int kTab = kWStem + 4 * 64 * 16;         // k_geo_init: one S's row-group table [42] x 16 B (NetParams::geo)
+constexpr int kTab = kWStem + 4 * 64 * 16;         // k_geo_init: one S's row-group table [42] x 16 B, or its row
+                                                   // table [128] x 16 B (NetParams::geo)
+constexpr int kTabRows = 128;                      // rows of a row table (8 tiles at S = 3)
 // The fused linear's B fragments: each wave loads its 6 k-steps straight into
 // registers at the head conv's start (an LDS-DMA copy made the compiler wait
 // vmcnt(0) at the head k-loop's first weight use).
@@ -130,8 +132,10 @@ struct NetParams {
     const float *b_pol;    // [7]
     const float *b_val;    // [1]
     // per group size S and row group idx (= LDS row / S): {cell, then the row group
-    // holding each 3x3 tap's neighbour cell as 9 bytes (0xFF off the board)} x 16 B
-    const uint4 *geo;             // [9][42]
+    // holding each 3x3 tap's neighbour cell as 9 bytes (0xFF off the board)} x 16 B;
+    // then per row-table size S = 2, 3 and LDS row: {position | cell << 8 (~0: a pad
+    // row), then the row of each tap's neighbour as 9 bytes (0xFF off the board)}
+    const uint4 *geo;             // [9][42] + [2][kTabRows] (geo_rows_at)
     const uint4 *lane_geo;        // per-lane geometry of every (S, wave, tile): lane_geo_at, k_geo_init
     unsigned long long *stamps;   // diagnostic: [grid][4 waves][kStamps] s_memtime, or null
     int blocks;
@@ -182,21 +186,33 @@ __device__ __forceinline__ uint32_t pack_relu_bf16x2(float a, float b) {
 
 // ---------------------------------------------------------------- cell order and skipped taps
 // Row layout of a group of S positions in the activation buffers:
-//  * S <= 3, position-major: row r holds cell r % 42 of position r / 42 (cell =
-//    board row * 7 + column), so a 3x3 tap is a contiguous shift of the rows;
+//  * S = 1, position-major: row r holds cell r (cell = board row * 7 + column), so a
+//    3x3 tap is a contiguous shift of the rows;
+//  * S = 2, 3, row table: row r holds position kRowTab[S - 2][r] / 42, cell
+//    kRowTab[S - 2][r] % 42, or is a pad row (255: its input is the zero block, its
+//    output is never read and no neighbour entry points at it), pads anywhere.
+//    (Cell-major rows cannot put an edge into a whole tile here: at S = 2 a tile
+//    would need 8 cells of one edge and the longest has 7, at S = 3 tile boundaries
+//    fall inside cells.)  One tile per board edge -- all four at S = 3; bottom, top
+//    and one side at S = 2 -- holds only rows of that edge, of any position, and
+//    drops the edge's 3 taps.  The table keeps row & 7 == (a * board row + b *
+//    column + c * position) & 7 with {a, b} = kRowLin[S - 2]: a tap shifts the
+//    residues of a tile's rows by one constant, which keeps the permuted B reads
+//    conflict-free (scripts/gen_cell_orders.py has the argument and counts them);
 //  * S >= 4, cell-major: row r holds cell kCellOrder[S][r / S] of position r % S.
 //    The orders group board-edge cells so that some 16-row position tiles have NO
-//    on-board neighbour for a tap: tap_skip(S, t) is the mask of such taps (bit
-//    (dh+1)*3 + (dw+1)) of tile t, and their MFMAs and B-fragment reads are skipped
-//    -- every product they would add is an exact zero (an out-of-board tap reads
-//    the zeroed block), so the results are the same.
+//    on-board neighbour for a tap.
+// tap_skip(S, t) is the mask of the taps (bit (dh+1)*3 + (dw+1)) for which no row of
+// tile t has an on-board neighbour; their MFMAs and B-fragment reads are skipped
+// -- every product they would add is an exact zero (an out-of-board tap reads
+// the zeroed block), so the results are the same.
 // Generated by scripts/gen_cell_orders.py (balanced over the four waves' task
 // plans; at S = 4 the order index's parity is the cell's checkerboard colour,
 // which keeps the permuted B reads conflict-free); max MFMA (tile, tap) pairs per
 // wave and layer:
 // S=1: position-major rows, identity order
-// S=2: position-major rows, identity order
-// S=3: position-major rows, identity order
+// S=2: row table, max MFMA tile-taps per wave and trunk layer 54 -> 45 [45, 45, 45, 45], head 45 -> 36; B-read bank conflicts 0
+// S=3: row table, max MFMA tile-taps per wave and trunk layer 72 -> 60 [60, 60, 60, 60], head 54 -> 45; B-read bank conflicts 0
 // S=4: max MFMA tile-taps per wave and trunk layer 90 -> 84 [84, 84, 84, 84], head 72 -> 72
 // S=5: max MFMA tile-taps per wave and trunk layer 126 -> 114 [114, 102, 114, 106], head 99 -> 84
 // S=6: max MFMA tile-taps per wave and trunk layer 144 -> 132 [128, 132, 132, 132], head 108 -> 99
@@ -213,10 +229,15 @@ constexpr uint8_t kCellOrder[9][42] = {   // host: packed into NetParams::geo at
     {8, 22, 4, 3, 1, 13, 20, 9, 33, 7, 21, 14, 25, 18, 19, 24, 35, 28, 0, 2, 5, 31, 32, 12, 16, 38, 36, 40, 39, 37, 26, 17, 27, 6, 34, 11, 30, 15, 23, 29, 10, 41},
     {28, 21, 41, 37, 18, 26, 1, 2, 16, 29, 22, 31, 15, 17, 5, 6, 24, 8, 13, 20, 4, 3, 33, 30, 27, 34, 0, 35, 12, 25, 23, 10, 36, 39, 19, 11, 32, 9, 38, 40, 7, 14},
 };
+constexpr uint8_t kRowTab[2][128] = {   // [S - 2]
+    {13, 54, 12, 58, 11, 52, 10, 51, 9, 50, 8, 53, 16, 57, 15, 55, 0, 255, 255, 44, 6, 47, 5, 46, 4, 45, 3, 48, 2, 43, 1, 42, 37, 78, 36, 77, 39, 80, 38, 83, 41, 82, 40, 81, 35, 255, 255, 79, 23, 64, 22, 67, 20, 61, 19, 60, 18, 59, 17, 62, 25, 66, 24, 65, 14, 255, 255, 49, 21, 255, 255, 70, 28, 255, 255, 63, 7, 255, 255, 56, 32, 73, 31, 76, 30, 71, 29, 69, 27, 68, 26, 72, 34, 75, 33, 74, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255},
+    {45, 5, 2, 44, 86, 46, 88, 85, 0, 87, 47, 89, 4, 1, 43, 3, 16, 50, 18, 23, 12, 9, 22, 11, 8, 29, 10, 15, 57, 17, 30, 19, 40, 37, 79, 39, 81, 123, 83, 125, 122, 82, 124, 121, 36, 78, 38, 80, 32, 66, 71, 52, 65, 25, 51, 64, 24, 58, 26, 31, 73, 33, 59, 72, 98, 21, 63, 7, 49, 91, 112, 35, 77, 42, 84, 105, 28, 70, 14, 56, 61, 95, 100, 68, 94, 54, 67, 93, 53, 74, 92, 60, 102, 99, 75, 101, 69, 13, 34, 76, 118, 41, 104, 48, 90, 111, 55, 97, 20, 62, 6, 27, 114, 119, 116, 255, 110, 107, 96, 109, 106, 103, 108, 113, 255, 115, 120, 117},
+};
+constexpr int8_t kRowLin[2][2] = {{4, 6}, {3, 5}};   // [S - 2]
 __host__ __device__ constexpr uint16_t tap_skip(int S, int t) {
     constexpr uint16_t m1[21] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    constexpr uint16_t m2[21] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    constexpr uint16_t m3[21] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    constexpr uint16_t m2[21] = {0, 7, 448, 0, 73, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    constexpr uint16_t m3[21] = {7, 0, 448, 0, 73, 0, 292, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     constexpr uint16_t m4[21] = {0, 0, 0, 7, 292, 0, 448, 73, 0, 0, 448, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     constexpr uint16_t m5[21] = {0, 0, 448, 0, 292, 7, 0, 0, 0, 73, 0, 0, 0, 295, 0, 0, 0, 0, 0, 0, 0};
     constexpr uint16_t m6[21] = {256, 0, 0, 448, 0, 0, 292, 0, 0, 7, 0, 0, 0, 0, 0, 73, 0, 0, 0, 0, 0};
@@ -225,6 +246,9 @@ __host__ __device__ constexpr uint16_t tap_skip(int S, int t) {
     return S == 1 ? m1[t] : S == 2 ? m2[t] : S == 3 ? m3[t] : S == 4 ? m4[t] : S == 5 ? m5[t] : S == 6 ? m6[t] : S == 7 ? m7[t] : m8[t];
 }
 __host__ __device__ constexpr bool cell_major(int S) { return S >= 4; }
+__host__ __device__ constexpr bool row_table(int S) { return S == 2 || S == 3; }
+// a row table's entries in NetParams::geo, in uint4
+__host__ __device__ constexpr int geo_rows_at(int S) { return 9 * c4::kCells + (S - 2) * kTabRows; }
 // head-feature row pitch (bf16 elements): the head conv's 8-B stores of a tile hit
 // distinct banks with 772 words at S = 8 and 776 words at S = 4
 __host__ __device__ constexpr int lin_pitch(int S) { return S == 4 ? 1552 : 1544; }
@@ -349,6 +373,10 @@ struct RowCell {
 };
 template <int S>
 __device__ __forceinline__ RowCell row_cell(const uint8_t *smem, int p) {
+    if constexpr (row_table(S)) {
+        const uint32_t e = ((const uint32_t *)(smem + kTab))[p * 4];
+        return e == ~0u ? RowCell{0, -1, 0} : RowCell{(int)(e & 255u), (int)(e >> 8), 0};
+    }
     if (p >= S * c4::kCells) return RowCell{0, -1, 0};
     if constexpr (!cell_major(S)) {
         const int s = p / c4::kCells, cell = p - s * c4::kCells;
@@ -366,7 +394,25 @@ __device__ __forceinline__ void make_geo(const uint8_t *smem, int lane, Geo<Plan
 #pragma unroll
     for (int t = 0; t < PL::NT; ++t) {
         const int p = PL::gpt(t) * 16 + col;
-        if constexpr (!cell_major(S)) {   // position-major rows: a tap is a contiguous shift
+        if constexpr (row_table(S)) {   // any row order through the staged table {position | cell, neighbour rows}
+            const uint4 e = *(const uint4 *)(smem + kTab + p * 16);
+            const bool real = e.x != ~0u;
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap) {
+                const uint32_t word = tap < 4 ? e.y : tap < 8 ? e.z : e.w;
+                const int nb = (int)((word >> (8 * (tap & 3))) & 255u);
+                int v;
+                if (real && nb != 255) {
+                    v = nb * 128 + ((q ^ (nb & 7)) << 4) + 256;
+                } else {   // the zero block, at the granule of the row residue an on-board neighbour would have
+                           // (row & 7 is linear in the cell's board row and column: kRowLin)
+                    const int r = (p + kRowLin[S - 2][0] * (tap / 3 - 1) + kRowLin[S - 2][1] * (tap % 3 - 1)) & 7;
+                    v = (r * 128 + ((q ^ r) << 4)) & 255;
+                }
+                if (tap & 1) g.rel2[t][tap >> 1] |= (uint32_t)v << 16;
+                else g.rel2[t][tap >> 1] = (uint32_t)v;
+            }
+        } else if constexpr (!cell_major(S)) {   // position-major rows: a tap is a contiguous shift
             const int cell = p % c4::kCells;
             const int h = cell / c4::kCols, w = cell - h * c4::kCols;
 #pragma unroll
@@ -469,9 +515,13 @@ __device__ void geo_init_s(const uint8_t *smem, uint4 *out, int W, int lane) {
 
 // one 64-thread workgroup per (S, wave): blockIdx.x = (S - 1) * 4 + W
 __global__ __launch_bounds__(64) void k_geo_init(const uint4 *__restrict__ geo, uint4 *__restrict__ out) {
-    __shared__ __attribute__((aligned(16))) uint8_t smem[kLdsBytes];
+    __shared__ __attribute__((aligned(16))) uint8_t smem[kTab + kTabRows * 16];
     const int S = blockIdx.x / kWaves + 1, W = blockIdx.x % kWaves, lane = threadIdx.x;
-    if (lane < c4::kCells) ((uint4 *)(smem + kTab))[lane] = geo[S * c4::kCells + lane];
+    if (row_table(S)) {
+        for (int r = lane; r < kTabRows; r += 64) ((uint4 *)(smem + kTab))[r] = geo[geo_rows_at(S) + r];
+    } else if (lane < c4::kCells) {
+        ((uint4 *)(smem + kTab))[lane] = geo[S * c4::kCells + lane];
+    }
     __syncthreads();
     switch (S) {
     case 1: geo_init_s<1>(smem, out, W, lane); break;
@@ -1455,8 +1505,11 @@ __host__ __device__ inline int group_size(uint32_t count, uint32_t grid) {
 // max(conc x CU cycles / grid, forward latency + kChainCycles) on the measured
 // per-group cycles (profiles/r04/search_ab/phases_pro.txt) is taken: larger
 // groups cost fewer CU cycles per leaf (29k at S = 1, 15.7k at S = 4, 12.6k at
-// S = 8).  The results do not depend on S.
-constexpr float kGroupCycles[kS + 1] = {0.f, 29200.f, 45500.f, 58600.f, 62900.f, 81200.f, 86200.f, 94700.f, 100500.f};
+// S = 8).  S = 1..3 were re-taken with the row tables' skipped taps as the old
+// entry x (new / parent group cycles) of one session, which keeps them on the
+// scale of the others (profiles/small_group_tapskip: 29.2k x 0.992, 45.5k x 0.956,
+// 58.6k x 0.888).  The results do not depend on S.
+constexpr float kGroupCycles[kS + 1] = {0.f, 29000.f, 43500.f, 52000.f, 62900.f, 81200.f, 86200.f, 94700.f, 100500.f};
 constexpr float kLaunchCycles = 4200.f;   // kernel entry to the first group (~2 us)
 #ifndef SPAI_CONC_CHAIN_CYCLES
 #define SPAI_CONC_CHAIN_CYCLES 31000.f
@@ -1857,7 +1910,7 @@ int net_create(spai_engine *e, int blocks, int hidden, const float *params, size
             }
     up(n->w_lin, wlin);
     // geometry table: per S and row group idx, the cell and each tap's neighbour row group
-    std::vector<uint32_t> geo((size_t)9 * c4::kCells * 4, 0);
+    std::vector<uint32_t> geo((size_t)geo_rows_at(4) * 4, 0);
     for (int S = 1; S <= kS; ++S) {
         int idx_of[c4::kCells];
         for (int i = 0; i < c4::kCells; ++i) idx_of[kCellOrder[S][i]] = i;
@@ -1870,6 +1923,27 @@ int net_create(spai_engine *e, int blocks, int hidden, const float *params, size
                 const bool ok = hh >= 0 && hh < c4::kRows && ww >= 0 && ww < c4::kCols;
                 const uint32_t nb = ok ? (uint32_t)idx_of[hh * c4::kCols + ww] : 255u;
                 e[1 + tap / 4] |= nb << (8 * (tap % 4));
+            }
+        }
+    }
+    for (int S = 2; S <= 3; ++S) {   // row tables
+        int row_of[3 * c4::kCells];
+        for (int r = 0; r < npt_of(S) * 16; ++r)
+            if (kRowTab[S - 2][r] != 255) row_of[kRowTab[S - 2][r]] = r;
+        for (int r = 0; r < kTabRows; ++r) {
+            uint32_t *e = &geo[((size_t)geo_rows_at(S) + r) * 4];
+            const int code = kRowTab[S - 2][r];   // position * 42 + cell
+            e[0] = ~0u;
+            e[1] = e[2] = e[3] = ~0u;
+            if (code == 255) continue;
+            const int s = code / c4::kCells, cell = code % c4::kCells, h = cell / c4::kCols, w = cell % c4::kCols;
+            e[0] = (uint32_t)s | (uint32_t)cell << 8;
+            for (int tap = 0; tap < 9; ++tap) {
+                const int hh = h + tap / 3 - 1, ww = w + tap % 3 - 1;
+                const bool ok = hh >= 0 && hh < c4::kRows && ww >= 0 && ww < c4::kCols;
+                if (!ok) continue;
+                const uint32_t nb = (uint32_t)row_of[s * c4::kCells + hh * c4::kCols + ww], sh = 8 * (tap % 4);
+                e[1 + tap / 4] = (e[1 + tap / 4] & ~(255u << sh)) | nb << sh;
             }
         }
     }
