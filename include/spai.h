@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define SPAI_VERSION_MAJOR 0
-#define SPAI_VERSION_MINOR 3
+#define SPAI_VERSION_MINOR 4
 
 typedef enum spai_error {
     SPAI_OK = 0,
@@ -596,10 +596,36 @@ int spai_chess_index_move(int side, int32_t index, uint16_t *move);
 /* net: model/chess.rs:48-77 (torso = stem + `blocks` residual blocks of 256
  * channels; policy head conv1x1 256->256 + ReLU + conv1x1 256->73; value head
  * conv1x1 256->1 + ReLU + linear 64->256 + ReLU + linear 256->1 + tanh).  params
- * in tch construction order as for spai_net_create.  bf16 MFMA, fp32 accumulate. */
+ * in tch construction order as for spai_net_create.  spai_chess_net_create builds
+ * the bf16 net (bf16 MFMA, fp32 accumulate): it is spai_chess_net_create_dtype with
+ * SPAI_DTYPE_BF16. */
 int spai_chess_net_num_params(int blocks, size_t *count);
 int spai_chess_net_init_params(int blocks, uint64_t seed, float *params);
 int spai_chess_net_create(spai_chess *e, int blocks, const float *params, size_t n_params, spai_chess_net **out);
+/* The same net in the arithmetic `dtype` (SPAI_DTYPE_BF16 or SPAI_DTYPE_F32; anything
+ * else is SPAI_ERR_INVALID).  An fp32 net is usable wherever a chess net is: forward,
+ * predict, spai_chess_set_net (search, self-play), a match player (the two players
+ * may differ in dtype), spai_chess_net_set_params.  It is the parity path, about
+ * 50 times slower than bf16 (profiles/chess_net_f32).  Its input planes are not rounded
+ * (planes 17 and 18 are fractions), and every output element is summed in one fixed
+ * order with separate multiply and add, so that a float32 restatement on the CPU
+ * (tests/chess_f32_ref.py) reproduces every logit and the value's pre-activation bit
+ * for bit:
+ *   3x3 convs   the conv bias first, then the products input channel ascending,
+ *               kernel row, kernel column; an off-board tap is skipped;
+ *   BatchNorm   unfolded, ((x - mean) * inv) * gamma + beta with inv =
+ *               1.0f / sqrtf(var + 1e-5f) computed on the host in float32;
+ *   residual    relu(h + bn(conv(...))), the block input h as the left operand;
+ *   heads       conv1x1 and linear outputs: the bias first, then the input index
+ *               ascending (policy conv1x1 256->256 + ReLU, conv1x1 256->73; value
+ *               conv1x1 256->1 + ReLU over the 64 cells, linear 64->256 + ReLU,
+ *               linear 256->1, tanhf).
+ * Only tanhf (and predict's expf) may differ from the host's libm in the last ulp.
+ * A position's result does not depend on its batch slot or on the rest of the batch. */
+int spai_chess_net_create_dtype(spai_chess *e, int blocks, const float *params, size_t n_params,
+                                int dtype /* spai_dtype */, spai_chess_net **out);
+/* the spai_dtype the net was created with */
+int spai_chess_net_dtype(spai_chess_net *net, int *dtype);
 int spai_chess_net_destroy(spai_chess_net *net);
 /* Net::forward(x, train=false): x [n][19][8][8] -> logits [n][4672], value [n] */
 int spai_chess_net_forward(spai_chess_net *net, uint32_t n, const float *x, float *logits, float *value);
@@ -645,8 +671,8 @@ int spai_chess_selfplay_stream(spai_chess *e, uint32_t n_games, uint32_t window,
 int spai_chess_set_timing(spai_chess *e, int enabled);
 int spai_chess_timing(spai_chess *e, double *avg_ms, double *launches, double *items);
 
-/* weight refresh of a self-play net in place (the BN fold + fragment pack of
- * spai_chess_net_create into the same allocations, stream-ordered behind any
+/* weight refresh of a self-play net of either dtype in place (the host packing of
+ * spai_chess_net_create / _create_dtype into the same allocations, stream-ordered behind any
  * search still reading the old weights): forward afterwards is bit-identical to
  * a net freshly created from the same parameters */
 int spai_chess_net_set_params(spai_chess_net *net, const float *params, size_t n_params);

@@ -259,6 +259,10 @@ extern "C" {
     pub fn spai_chess_apply(e: *mut spai_chess, first: u32, n: u32, moves: *const u16, rc: *mut i32) -> c_int;
     pub fn spai_chess_net_create(e: *mut spai_chess, blocks: c_int, params: *const f32, n: usize,
                                  out: *mut *mut spai_chess_net) -> c_int;
+    /// dtype: spai_dtype (0 = bf16, what spai_chess_net_create builds; 1 = f32, the parity path)
+    pub fn spai_chess_net_create_dtype(e: *mut spai_chess, blocks: c_int, params: *const f32, n: usize,
+                                       dtype: c_int, out: *mut *mut spai_chess_net) -> c_int;
+    pub fn spai_chess_net_dtype(net: *mut spai_chess_net, dtype: *mut c_int) -> c_int;
     pub fn spai_chess_net_destroy(net: *mut spai_chess_net) -> c_int;
     pub fn spai_chess_net_forward(net: *mut spai_chess_net, n: u32, x: *const f32, logits: *mut f32, value: *mut f32)
         -> c_int;

@@ -1,12 +1,17 @@
 """Chess matches between two evaluators on the device (ChessEngine.match, spai_chess_match_run).
 
   python scripts/chess_match.py A B [--games N] [--sims-a K] [--sims-b K] [--blocks B]
+                                    [--dtype-a {bf16,f32}] [--dtype-b {bf16,f32}]
                                     [--opening-plies P] [--max-plies M] [--seed S] [--max-trees T]
 
 A and B are each a safetensors checkpoint (spai_params_load_safetensors), or one of
   init:<seed>   the random initial weights of that seed
   uniform       plain MCTS on uniform priors and value 0, without a network
   hash          the deterministic hash evaluator of the parity tests
+--dtype-a / --dtype-b choose the arithmetic of a net player (ChessNet's dtype, default
+bf16): `ckpt ckpt --dtype-b f32` plays one checkpoint's bf16 net against its own
+unquantised fp32 net, i.e. measures what bf16 costs it in Elo.  The fp32 net is the
+parity path, about 50 times slower (profiles/chess_net_f32): keep --sims and --blocks small.
 Prints one JSON line: wins, draws and losses of A split by who moved first, the
 games adjudicated a draw at --max-plies, A's score, the Elo difference (A - B) with
 a 95 % interval from the trinomial counts (scripts/c4_match.py's arithmetic), and
@@ -40,7 +45,12 @@ from c4_match import elo_from_counts  # noqa: E402  (the scoring is Connect4's, 
 COUNTS = ("a_wins", "draws", "b_wins", "sims", "evals")
 
 
-def make_player(sc, eng, spec, sims, blocks):
+def describe(spec, dtype):
+    """a player as the report names it: net players with their dtype"""
+    return spec if spec in ("uniform", "hash") else f"{spec} ({dtype})"
+
+
+def make_player(sc, eng, spec, sims, blocks, dtype="bf16"):
     import spai
     if spec == "uniform":
         return (sc.EVAL_UNIFORM, None, sims)
@@ -50,7 +60,7 @@ def make_player(sc, eng, spec, sims, blocks):
         params = sc.init_params(blocks, int(spec[5:]))
     else:
         params = spai.load_params(spec, blocks, 256, game=sc.GAME_CHESS, n=sc.num_params(blocks))
-    return (sc.EVAL_NET, sc.ChessNet(eng, blocks, params), sims)
+    return (sc.EVAL_NET, sc.ChessNet(eng, blocks, params, dtype=dtype), sims)
 
 
 def report(tot, games, seconds):
@@ -157,6 +167,8 @@ def parser():
     ap.add_argument("--sims-a", type=int, default=400)
     ap.add_argument("--sims-b", type=int, default=400)
     ap.add_argument("--blocks", type=int, default=20)
+    ap.add_argument("--dtype-a", choices=("bf16", "f32"), default="bf16")
+    ap.add_argument("--dtype-b", choices=("bf16", "f32"), default="bf16")
     ap.add_argument("--opening-plies", type=int, default=2)
     ap.add_argument("--max-plies", type=int, default=512)
     ap.add_argument("--seed", type=int, default=0)
@@ -180,9 +192,9 @@ def main(argv=None):
     per_call = max(1, min(args.games, args.max_trees // 2))
     eng = sc.ChessEngine(num_searches=max(args.sims_a, args.sims_b), max_trees=2 * per_call,
                          eval_kind=sc.EVAL_UNIFORM)
-    a = make_player(sc, eng, args.a, args.sims_a, args.blocks)
-    b = make_player(sc, eng, args.b, args.sims_b, args.blocks)
-    out = dict(a=args.a, b=args.b, sims_a=args.sims_a, sims_b=args.sims_b, opening_plies=args.opening_plies,
+    a = make_player(sc, eng, args.a, args.sims_a, args.blocks, args.dtype_a)
+    b = make_player(sc, eng, args.b, args.sims_b, args.blocks, args.dtype_b)
+    out = dict(a=describe(args.a, args.dtype_a), b=describe(args.b, args.dtype_b), sims_a=args.sims_a, sims_b=args.sims_b, opening_plies=args.opening_plies,
                max_plies=args.max_plies, blocks=args.blocks, seed=args.seed)
     out.update(play(eng, a, b, args.games, per_call, args.opening_plies, args.max_plies, args.seed))
     print(json.dumps(out))

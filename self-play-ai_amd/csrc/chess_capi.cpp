@@ -53,6 +53,7 @@ void release_all(spai_chess *e) {
     B.counts.release();
     B.tree.release();
     B.x.release();
+    B.xf.release();
     B.logits.release();
     B.value.release();
     e->active.release();
@@ -223,9 +224,21 @@ int spai_chess_net_init_params(int blocks, uint64_t seed, float *params) {
 }
 
 int spai_chess_net_create(spai_chess *e, int blocks, const float *params, size_t n_params, spai_chess_net **out) {
+    return spai_chess_net_create_dtype(e, blocks, params, n_params, SPAI_DTYPE_BF16, out);
+}
+
+int spai_chess_net_create_dtype(spai_chess *e, int blocks, const float *params, size_t n_params, int dtype,
+                                spai_chess_net **out) {
     CH_CHECK(e);
     SPAI_PTR(out);
-    return net_create(e, blocks, params, n_params, out);
+    return net_create(e, blocks, params, n_params, dtype, out);
+}
+
+int spai_chess_net_dtype(spai_chess_net *net, int *dtype) {
+    SPAI_PTR(net);
+    SPAI_PTR(dtype);
+    *dtype = net->dtype;
+    return SPAI_OK;
 }
 
 int spai_chess_net_destroy(spai_chess_net *net) {

@@ -48,6 +48,7 @@ struct Batch {
     DevBuf<uint32_t> counts;    // [num_searches] per-iteration leaf counters
     DevBuf<uint32_t> tree;      // slot -> tree
     DevBuf<uint16_t> x;         // [cap][64 cells][kInCh] bf16 net input
+    DevBuf<float> xf;           // [cap][19][64] fp32 net input: only once an fp32 net is attached (batch_attach)
     DevBuf<float> logits;       // [cap][kPolicy]
     DevBuf<float> value;        // [cap]
 };
@@ -106,6 +107,10 @@ struct spai_chess {
 struct spai_chess_net {
     spai_chess *eng = nullptr;
     int blocks = 0;
+    int dtype = SPAI_DTYPE_BF16;   // spai_dtype
+    // SPAI_DTYPE_F32: the raw fp32 weights in chess_net_f32.hip's layout, and none of the bf16 buffers below
+    spai::DevBuf<float> wf;
+    spai::DevBuf<float> io_xf;     // [io_cap][19][64] fp32 input of forward / predict
     // packed, BN-folded bf16 MFMA A-fragments and fp32 biases (chess_net.hip)
     spai::DevBuf<uint16_t> w_stem, w_res, w_p1, w_p2;
     spai::DevBuf<float> b_stem, b_res, b_p1, b_p2;
@@ -141,14 +146,22 @@ int get_action_host(int side, int index);
 // chess_net.hip
 size_t net_num_params(int blocks);
 void net_init_params(int blocks, uint64_t seed, float *params);
-int net_create(spai_chess *e, int blocks, const float *params, size_t n, spai_chess_net **out);
+int net_create(spai_chess *e, int blocks, const float *params, size_t n, int dtype, spai_chess_net **out);
 void net_destroy(spai_chess_net *net);
 int net_set_params(spai_chess_net *net, const float *params, size_t n);
-// evaluate `count` (device scalar) positions of x [max_n][64][kInCh] bf16
+// evaluate `count` (device scalar) positions: a bf16 net reads x [max_n][64][kInCh] bf16,
+// an fp32 net xf [max_n][19][64] fp32 (the other pointer is not read)
 int net_eval(spai_chess_net *net, hipStream_t st, const uint32_t *d_count, uint32_t max_n, const uint16_t *x,
-             float *logits, float *value);
+             const float *xf, float *logits, float *value);
+// the batch's fp32 input, allocated once an fp32 net evaluates its leaves (never inside a ply loop)
+int batch_attach(Batch &b, const spai_chess_net *net);
 int net_forward_host(spai_chess_net *net, uint32_t n, const float *x, float *logits, float *value);
 int net_predict(spai_chess_net *net, uint32_t first, uint32_t n, float *priors, float *values);
+
+// chess_net_f32.hip
+void net_f32_pack(int blocks, const float *params, std::vector<float> &buf);
+int net_f32_launch(spai_chess_net *net, hipStream_t st, const uint32_t *d_count, uint32_t max_n, const float *xf,
+                   float *logits, float *value);
 
 // chess_search.hip
 int trees_create(spai_chess *e, uint32_t n);

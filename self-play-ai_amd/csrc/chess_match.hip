@@ -229,6 +229,7 @@ void match_release(spai_chess *e) {
     B.counts.release();
     B.tree.release();
     B.x.release();
+    B.xf.release();
     B.logits.release();
     B.value.release();
     B.cap = 0;
@@ -324,6 +325,8 @@ int match_run(spai_chess *e, const spai_chess_match_player *a, const spai_chess_
     // the leaf counters sized now: an allocation inside the ply loop would join the device
     for (int p = 0; p < 2; ++p)
         if (side[p].batch->counts.n < side[p].sims) SPAI_TRY(side[p].batch->counts.alloc(side[p].sims));
+    // likewise the fp32 planes of a chain whose player's net is fp32 (each chain follows its own net)
+    for (int p = 0; p < 2; ++p) SPAI_TRY(batch_attach(*side[p].batch, side[p].net));
     uint32_t *const *list = M.h_list;
     uint4 *const *hrec = M.h_rec;
     double sims[2] = {0, 0}, evals[2] = {0, 0};

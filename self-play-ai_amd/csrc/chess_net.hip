@@ -647,7 +647,39 @@ int pack_params(int blocks, const float *params, size_t n, Packed &K) {
 }
 }  // namespace
 
-int net_create(spai_chess *e, int blocks, const float *params, size_t n, spai_chess_net **out) {
+namespace {
+int check_params(int blocks, const float *params, size_t n) {
+    SPAI_CHECK(blocks >= 0 && blocks <= kMaxBlocks, SPAI_ERR_UNSUPPORTED, "chess net: 0..%d blocks (got %d)",
+               kMaxBlocks, blocks);
+    SPAI_CHECK(params && n == net_num_params(blocks), SPAI_ERR_INVALID, "expected %zu params, got %zu",
+               net_num_params(blocks), n);
+    return SPAI_OK;
+}
+}  // namespace
+
+int net_create(spai_chess *e, int blocks, const float *params, size_t n, int dtype, spai_chess_net **out) {
+    SPAI_CHECK(dtype == SPAI_DTYPE_BF16 || dtype == SPAI_DTYPE_F32, SPAI_ERR_INVALID, "bad net dtype %d", dtype);
+    if (dtype == SPAI_DTYPE_F32) {
+        // the raw fp32 weights in chess_net_f32.hip's layout; no bf16 fragments
+        SPAI_TRY(check_params(blocks, params, n));
+        std::vector<float> buf;
+        net_f32_pack(blocks, params, buf);
+        spai_chess_net *net = new spai_chess_net();
+        net->eng = e;
+        net->blocks = blocks;
+        net->dtype = dtype;
+        int rc = net->wf.alloc(buf.size());
+        if (rc == SPAI_OK && hipMemcpy(net->wf.p, buf.data(), buf.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+            set_error("chess net: weight upload failed");
+            rc = SPAI_ERR_DEVICE;
+        }
+        if (rc != SPAI_OK) {
+            net_destroy(net);
+            return rc;
+        }
+        *out = net;
+        return SPAI_OK;
+    }
     Packed K;
     SPAI_TRY(pack_params(blocks, params, n, K));
     spai_chess_net *net = new spai_chess_net();
@@ -691,9 +723,19 @@ int net_create(spai_chess *e, int blocks, const float *params, size_t n, spai_ch
 int net_set_params(spai_chess_net *net, const float *params, size_t n) {
     SPAI_CHECK(params && n == net_num_params(net->blocks), SPAI_ERR_INVALID, "expected %zu params, got %zu",
                net_num_params(net->blocks), n);
+    hipStream_t st = net->eng->stream;
+    if (net->dtype == SPAI_DTYPE_F32) {
+        std::vector<float> buf;
+        net_f32_pack(net->blocks, params, buf);
+        SPAI_CHECK(net->wf.n == buf.size(), SPAI_ERR_INVALID, "net allocation does not match");
+        const hipError_t ce = hipMemcpyAsync(net->wf.p, buf.data(), buf.size() * 4, hipMemcpyHostToDevice, st);
+        const hipError_t se = hipStreamSynchronize(st);   // the host vector dies here
+        SPAI_HIP(ce);
+        SPAI_HIP(se);
+        return SPAI_OK;
+    }
     Packed K;
     SPAI_TRY(pack_params(net->blocks, params, n, K));
-    hipStream_t st = net->eng->stream;
     auto put16 = [&](DevBuf<uint16_t> &d, const std::vector<uint16_t> &h) -> int {
         SPAI_CHECK(d.n == h.size(), SPAI_ERR_INVALID, "net allocation does not match");
         SPAI_HIP(hipMemcpyAsync(d.p, h.data(), h.size() * 2, hipMemcpyHostToDevice, st));
@@ -729,7 +771,7 @@ void net_destroy(spai_chess_net *net) {
     if (!net) return;
     for (auto *d : {&net->w_stem, &net->w_res, &net->w_p1, &net->w_p2, &net->io_x}) d->release();
     for (auto *d : {&net->b_stem, &net->b_res, &net->b_p1, &net->b_p2, &net->v_w, &net->v_b, &net->l1_w, &net->l1_b,
-                    &net->l2_w, &net->l2_b, &net->io_logits, &net->io_value})
+                    &net->l2_w, &net->l2_b, &net->io_logits, &net->io_value, &net->wf, &net->io_xf})
         d->release();
     net->io_count.release();
     delete net;
@@ -756,8 +798,9 @@ static NetW weights_of(const spai_chess_net *n) {
 }
 
 int net_eval(spai_chess_net *net, hipStream_t st, const uint32_t *d_count, uint32_t max_n, const uint16_t *x,
-             float *logits, float *value) {
+             const float *xf, float *logits, float *value) {
     if (!max_n) return SPAI_OK;
+    if (net->dtype == SPAI_DTYPE_F32) return net_f32_launch(net, st, d_count, max_n, xf, logits, value);
     const uint32_t n_cu = (uint32_t)net->eng->n_cu;
     k_chess_forward<<<std::min(max_n, n_cu), kThreads, 0, st>>>(d_count, max_n, n_cu, x, weights_of(net), logits,
                                                                value);
@@ -765,20 +808,44 @@ int net_eval(spai_chess_net *net, hipStream_t st, const uint32_t *d_count, uint3
     return SPAI_OK;
 }
 
+namespace {
+// forward / predict staging for n positions: the bf16 input of a bf16 net, the fp32 input of an fp32 one
+int io_reserve(spai_chess_net *net, uint32_t n) {
+    if (net->io_cap >= n) return SPAI_OK;
+    if (net->dtype == SPAI_DTYPE_F32) SPAI_TRY(net->io_xf.alloc((size_t)n * kPlanes * 64));
+    else SPAI_TRY(net->io_x.alloc((size_t)n * 64 * kInCh));
+    SPAI_TRY(net->io_logits.alloc((size_t)n * kPolicy));
+    SPAI_TRY(net->io_value.alloc(n));
+    net->io_cap = n;
+    return SPAI_OK;
+}
+}  // namespace
+
+int batch_attach(Batch &b, const spai_chess_net *net) {
+    if (!net || net->dtype != SPAI_DTYPE_F32) return SPAI_OK;
+    const size_t need = (size_t)b.cap * kPlanes * 64;
+    if (b.xf.n != need) SPAI_TRY(b.xf.alloc(need));
+    return SPAI_OK;
+}
+
 int net_forward_host(spai_chess_net *net, uint32_t n, const float *x, float *logits, float *value) {
     if (!n) return SPAI_OK;
     spai_chess *e = net->eng;
-    if (net->io_cap < n) {
-        SPAI_TRY(net->io_x.alloc((size_t)n * 64 * kInCh));
-        SPAI_TRY(net->io_logits.alloc((size_t)n * kPolicy));
-        SPAI_TRY(net->io_value.alloc(n));
-        net->io_cap = n;
+    SPAI_TRY(io_reserve(net, n));
+    if (net->dtype == SPAI_DTYPE_F32) {   // the fp32 encoding is the kernel's input as it stands
+        SPAI_HIP(hipMemcpyAsync(net->io_xf.p, x, sizeof(float) * n * kPlanes * 64, hipMemcpyHostToDevice, e->stream));
+        SPAI_TRY(net_eval(net, e->stream, nullptr, n, nullptr, net->io_xf.p, net->io_logits.p, net->io_value.p));
+        SPAI_HIP(hipMemcpyAsync(logits, net->io_logits.p, sizeof(float) * n * kPolicy, hipMemcpyDeviceToHost,
+                                e->stream));
+        SPAI_HIP(hipMemcpyAsync(value, net->io_value.p, sizeof(float) * n, hipMemcpyDeviceToHost, e->stream));
+        SPAI_HIP(hipStreamSynchronize(e->stream));
+        return SPAI_OK;
     }
     float *d_in = net->io_logits.p;   // f32 input staged in the logits buffer (n*1216 <= n*4672)
     SPAI_HIP(hipMemcpyAsync(d_in, x, sizeof(float) * n * kPlanes * 64, hipMemcpyHostToDevice, e->stream));
     k_pack_input<<<(n * 64 + 255) / 256, 256, 0, e->stream>>>(d_in, n, net->io_x.p);
     SPAI_HIP(hipGetLastError());
-    SPAI_TRY(net_eval(net, e->stream, nullptr, n, net->io_x.p, net->io_logits.p, net->io_value.p));
+    SPAI_TRY(net_eval(net, e->stream, nullptr, n, net->io_x.p, nullptr, net->io_logits.p, net->io_value.p));
     SPAI_HIP(hipMemcpyAsync(logits, net->io_logits.p, sizeof(float) * n * kPolicy, hipMemcpyDeviceToHost, e->stream));
     SPAI_HIP(hipMemcpyAsync(value, net->io_value.p, sizeof(float) * n, hipMemcpyDeviceToHost, e->stream));
     SPAI_HIP(hipStreamSynchronize(e->stream));
@@ -793,17 +860,16 @@ int net_predict(spai_chess_net *net, uint32_t first, uint32_t n, float *priors, 
     spai_chess *e = net->eng;
     SPAI_CHECK((uint64_t)first + n <= e->slots.n, SPAI_ERR_INVALID, "slots [%u, %u) out of range (%u)", first,
                first + n, e->slots.n);
-    if (net->io_cap < n) {
-        SPAI_TRY(net->io_x.alloc((size_t)n * 64 * kInCh));
-        SPAI_TRY(net->io_logits.alloc((size_t)n * kPolicy));
-        SPAI_TRY(net->io_value.alloc(n));
-        net->io_cap = n;
-    }
+    SPAI_TRY(io_reserve(net, n));
     float *d_enc = e->slots.f32.p, *d_pri = e->slots.f32b.p;
     SPAI_TRY(slots_encode_device(e, first, n, d_enc));
-    k_pack_input<<<(n * 64 + 255) / 256, 256, 0, e->stream>>>(d_enc, n, net->io_x.p);
-    SPAI_HIP(hipGetLastError());
-    SPAI_TRY(net_eval(net, e->stream, nullptr, n, net->io_x.p, net->io_logits.p, net->io_value.p));
+    if (net->dtype == SPAI_DTYPE_F32) {   // the fp32 encoding is the kernel's input as it stands
+        SPAI_TRY(net_eval(net, e->stream, nullptr, n, nullptr, d_enc, net->io_logits.p, net->io_value.p));
+    } else {
+        k_pack_input<<<(n * 64 + 255) / 256, 256, 0, e->stream>>>(d_enc, n, net->io_x.p);
+        SPAI_HIP(hipGetLastError());
+        SPAI_TRY(net_eval(net, e->stream, nullptr, n, net->io_x.p, nullptr, net->io_logits.p, net->io_value.p));
+    }
     SPAI_TRY(slots_softmax_mask_device(e, first, n, net->io_logits.p, d_pri));
     SPAI_HIP(hipMemcpyAsync(priors, d_pri, sizeof(float) * n * kPolicy, hipMemcpyDeviceToHost, e->stream));
     SPAI_HIP(hipMemcpyAsync(values, net->io_value.p, sizeof(float) * n, hipMemcpyDeviceToHost, e->stream));

@@ -33,6 +33,7 @@ namespace {
 struct BV {
     uint32_t *tree;
     uint16_t *x;
+    float *xf;   // fp32 planes [slot][19][64] for an fp32 net, else null
     float *logits, *value;
 };
 
@@ -172,6 +173,11 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_cleaf(TV T, BV B, const
         uint4 *dst = (uint4 *)(B.x + ((size_t)slot * 64 + lane) * kInCh);
 #pragma unroll
         for (int k = 0; k < kInCh / 8; ++k) dst[k] = make_uint4(pk[4 * k], pk[4 * k + 1], pk[4 * k + 2], pk[4 * k + 3]);
+        if (B.xf) {   // an fp32 net reads the planes unrounded (spai_chess_encode's layout)
+            float *xf = B.xf + (size_t)slot * kPlanes * 64 + lane;
+#pragma unroll
+            for (int p = 0; p < kPlanes; ++p) xf[p * 64] = v[p];
+        }
     }
 }
 
@@ -497,6 +503,7 @@ BV bview(const Batch &b) {
     BV B;
     B.tree = b.tree.p;
     B.x = b.x.p;
+    B.xf = nullptr;
     B.logits = b.logits.p;
     B.value = b.value.p;
     return B;
@@ -600,9 +607,13 @@ int chain_launch(spai_chess *e, const Chain &C) {
     if (B.counts.n < sims) SPAI_TRY(B.counts.alloc(sims));
     SPAI_HIP(hipMemsetAsync(B.counts.p, 0, sizeof(uint32_t) * sims, C.stream));
     const TV T = view(e);
-    const BV BVv = bview(B);
+    BV BVv = bview(B);
     const int kind = C.kind;
     SPAI_CHECK(kind != SPAI_EVAL_NET || C.net, SPAI_ERR_INVALID, "cfg.eval = NET but no net set (spai_chess_set_net)");
+    if (kind == SPAI_EVAL_NET && C.net->dtype == SPAI_DTYPE_F32) {
+        SPAI_TRY(batch_attach(B, C.net));   // allocates on the chain's first fp32 search only
+        BVv.xf = B.xf.p;
+    }
     k_ccompact<<<blocks_for(na), 64 * kWavesPerBlock, 0, C.stream>>>(T, C.active, na, sims * kMaxChildren, C.err);
     SPAI_HIP(hipGetLastError());
     KernelTimer *tm = C.timer;
@@ -625,7 +636,7 @@ int chain_launch(spai_chess *e, const Chain &C) {
         if (timed) SPAI_TRY(stamp(0, false));
         if (kind == SPAI_EVAL_NET) {
             if (timed) SPAI_TRY(stamp(1, true));
-            SPAI_TRY(net_eval(C.net, C.stream, cnt, na, B.x.p, B.logits.p, B.value.p));
+            SPAI_TRY(net_eval(C.net, C.stream, cnt, na, B.x.p, BVv.xf, B.logits.p, B.value.p));
             if (timed) SPAI_TRY(stamp(1, false));
         }
         if (timed) SPAI_TRY(stamp(2, true));

@@ -74,6 +74,8 @@ def lib():
         L.spai_chess_net_num_params.argtypes = [i32, P(C.c_size_t)]
         L.spai_chess_net_init_params.argtypes = [i32, u64, vp]
         L.spai_chess_net_create.argtypes = [vp, i32, vp, C.c_size_t, P(vp)]
+        L.spai_chess_net_create_dtype.argtypes = [vp, i32, vp, C.c_size_t, i32, P(vp)]
+        L.spai_chess_net_dtype.argtypes = [vp, P(i32)]
         L.spai_chess_net_destroy.argtypes = [vp]
         L.spai_chess_net_forward.argtypes = [vp, u32, vp, vp, vp]
         L.spai_chess_predict.argtypes = [vp, u32, u32, vp, vp]
@@ -394,13 +396,27 @@ class ChessEngine:
 
 
 class ChessNet:
-    def __init__(self, eng, blocks, params):
+    """dtype "bf16" (the default: the MFMA throughput path) or "f32": the reference's own
+    fp32 arithmetic on unrounded input planes, every output summed in one fixed order
+    (spai.h), bit-exact against tests/chess_f32_ref.py and about 50 times slower
+    (profiles/chess_net_f32).  Either kind serves forward, predict, search, self-play and match."""
+    DTYPES = {"bf16": 0, "f32": 1}   # spai_dtype
+
+    def __init__(self, eng, blocks, params, dtype="bf16"):
+        if dtype not in self.DTYPES:
+            raise ValueError(f"dtype {dtype!r}: 'bf16' or 'f32'")
         p = np.ascontiguousarray(params, np.float32)
         h = C.c_void_p()
-        _check(lib().spai_chess_net_create(eng.h, blocks, _p(p), p.size, C.byref(h)))
+        if dtype == "bf16":
+            _check(lib().spai_chess_net_create(eng.h, blocks, _p(p), p.size, C.byref(h)))
+        else:
+            _check(lib().spai_chess_net_create_dtype(eng.h, blocks, _p(p), p.size, self.DTYPES[dtype], C.byref(h)))
         self.h = h
         self.eng = eng
         self.blocks = blocks
+        d = C.c_int()
+        _check(lib().spai_chess_net_dtype(h, C.byref(d)))
+        self.dtype = {v: k for k, v in self.DTYPES.items()}[d.value]
 
     def close(self):
         if getattr(self, "h", None):
