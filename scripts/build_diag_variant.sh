@@ -1,5 +1,5 @@
 # build_exp/libspai_diag_<tag>.so: the diagnostic (phase-stamp) library with
-# net_c4.hip under extra flags, e.g. the timing-only deletion experiments
+# net_c4.hip under extra flags, e.g. -DSPAI_DIAG_KSTEP
 # usage: scripts/build_diag_variant.sh tag "-DFLAG ..." [tag "-D..."]...
 set -e
 # UNROLL: extra unroll flags for the variant (e.g. -mllvm -pragma-unroll-threshold=1000000)

@@ -1,5 +1,5 @@
 # forward phase stamps (scripts/net_phases.py) for each diagnostic library variant
-#   VARIANTS="base noa nob" TAG=x bash scripts/gpu_diag_phases.sh
+#   VARIANTS="base head entry" TAG=x bash scripts/gpu_diag_phases.sh
 set -o pipefail
 cd $GRAFT_REPO_ROOT && export TMPDIR=/tmp && O=gpurun_out/${TAG:-diag} && mkdir -p $O
 for v in ${VARIANTS:-base}; do

@@ -1,5 +1,5 @@
 # learner throughput A/B: the in-tree build against build_exp/libspai_<v>.so variants
-# (scripts/build_learner_variant.sh), base measured first and last
+# (scripts/build_variant.sh learner.hip ...), base measured first and last
 cd $GRAFT_REPO_ROOT && O=gpurun_out/lvar2 && mkdir -p $O
 for v in base ${VARIANTS:-} base; do
   if [ $v = base ]; then unset SPAI_LIB; else export SPAI_LIB=$PWD/build_exp/libspai_$v.so; fi

@@ -14,23 +14,30 @@ import tempfile
 B = "/opt/rocm/lib/llvm/bin"
 
 
+def code_objects(path, tmp):
+    """paths of the gfx950 code objects of a built library or object, unbundled into directory tmp"""
+    fb = os.path.join(tmp, "fb.bin")
+    subprocess.run([f"{B}/llvm-objcopy", f"--dump-section=.hip_fatbin={fb}", path, os.path.join(tmp, "s")], check=True)
+    data = open(fb, "rb").read()
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    starts = [m.start() for m in re.finditer(re.escape(magic), data)]
+    out = []
+    for i, s in enumerate(starts):
+        part = os.path.join(tmp, f"b{i}")
+        open(part, "wb").write(data[s:starts[i + 1] if i + 1 < len(starts) else len(data)])
+        co = part + ".co"
+        r = subprocess.run([f"{B}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={part}",
+                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], capture_output=True)
+        if r.returncode == 0:
+            out.append(co)
+    return out
+
+
 def kernels(path):
     """{kernel name: descriptor fields} of every gfx950 kernel in a built library"""
     out = {}
     with tempfile.TemporaryDirectory() as t:
-        fb = os.path.join(t, "fb.bin")
-        subprocess.run([f"{B}/llvm-objcopy", f"--dump-section=.hip_fatbin={fb}", path, os.path.join(t, "s")], check=True)
-        data = open(fb, "rb").read()
-        magic = b"__CLANG_OFFLOAD_BUNDLE__"
-        starts = [m.start() for m in re.finditer(re.escape(magic), data)]
-        for i, s in enumerate(starts):
-            part = os.path.join(t, f"b{i}")
-            open(part, "wb").write(data[s:starts[i + 1] if i + 1 < len(starts) else len(data)])
-            co = part + ".co"
-            r = subprocess.run([f"{B}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={part}",
-                                "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], capture_output=True)
-            if r.returncode:
-                continue
+        for co in code_objects(path, t):
             notes = subprocess.run([f"{B}/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
             for ent in notes.split("  - .agpr_count:")[1:]:
                 f = dict(re.findall(r"\.(\w+):\s+(\S+)", ent))

@@ -45,10 +45,7 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef short i16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kHid = 256;
-#ifndef SPAI_CHESS_WAVES
-#define SPAI_CHESS_WAVES 4   // 8 (two per SIMD) measured equal: 2.101 vs 2.101 ms
-#endif
-constexpr int kWaves = SPAI_CHESS_WAVES;     // 4: one wave per SIMD; 8: two
+constexpr int kWaves = 4;                     // one wave per SIMD (8, two per SIMD, measured equal: 2.101 vs 2.101 ms)
 constexpr int kCPW = 16 / kWaves;             // co tiles (of 16 channels) per wave
 constexpr int kThreads = 64 * kWaves;
 constexpr int kPos = 2;                       // positions per workgroup
@@ -92,45 +89,21 @@ __device__ __forceinline__ int row_chunk(int v, int c) { return v * kStride + (c
 // Software pipeline (fully unrolled, so every ring slot is static): weight
 // fragments (global/L2) DA-1 k-steps ahead, activation fragments (LDS) one
 // k-step ahead; the first k-step takes the bias as its C operand.
-#ifndef SPAI_CHESS_DA
-#define SPAI_CHESS_DA 4   // weight ring: 3 k-steps ahead (measured: 2 -> 3.40 ms, 8 -> 2.19 ms at 4 waves)
-#endif
-#ifndef SPAI_CHESS_DB
-#define SPAI_CHESS_DB 2
-#endif
-#ifndef SPAI_CHESS_SCHED
-#define SPAI_CHESS_SCHED 0
-#endif
-#ifndef SPAI_CHESS_PIN
-#define SPAI_CHESS_PIN 1
-#endif
-#ifndef SPAI_CHESS_TAP_UNROLL
-#define SPAI_CHESS_TAP_UNROLL 9   // taps per iteration of the tap loop (9: fully unrolled, 1.92 vs 1.99 ms)
-#endif
-// SPAI_CHESS_PREFETCH (experiment): at a conv's start every wave loads its
-// share of the NEXT conv's weight fragments (the 128 waves of an XCD split the
-// layer's 72 x 16 fragments), so that layer's ring loads hit the XCD's L2
-// instead of going to the Infinity Cache one k-step window ahead; the loads'
-// values feed a never-taken store, so they are waited for once, early in this conv.
+constexpr int kDA = 4;   // weight ring: 3 k-steps ahead (measured: 2 -> 3.40 ms, 8 -> 2.19 ms at 4 waves)
+constexpr int kDB = 2;   // activation ring
+constexpr int kTapUnroll = 9;   // taps per iteration of the tap loop (9: fully unrolled, 1.92 vs 1.99 ms)
+// `wnext` (the next conv's weights, or null) is unused: it fed a retired experiment that
+// prefetched the next layer's weights into L2.  It stays for now because k_chess_forward's
+// compiled bytes change (same size) when the second trunk conv's argument expression goes,
+// and the retirement kept every kernel's device code identical
+// (profiles/variant_retirement).  Drop it with the next change that moves this kernel's
+// code anyway.
 template <int TAPS, int CB, int NT>
 __device__ __forceinline__ void conv(const uint8_t *smem, int in, const uint4 *__restrict__ w,
                                      const float *__restrict__ bias, int wave, int lane, f32x4 (&acc)[kCPW][NT],
-                                     const uint4 *__restrict__ wnext = nullptr, float *__restrict__ sink = nullptr) {
-    constexpr int DA = SPAI_CHESS_DA;
-#ifdef SPAI_CHESS_PREFETCH
-    uint32_t pf = 0;
-    if (wnext) {
-        const int g = (int)((blockIdx.x >> 3) & 31u) * kWaves + wave;   // blocks b, b + 8, ... share an XCD
-#pragma unroll
-        for (int j = 0; j < (72 * kCT + 127) / 128; ++j) {
-            const int f = g + 128 * j;
-            if (f < 72 * kCT) pf ^= wnext[(size_t)f * kFrag + lane].x;
-        }
-    }
-#else
+                                     const uint4 *__restrict__ wnext = nullptr) {
+    constexpr int DA = kDA;
     (void)wnext;
-    (void)sink;
-#endif
     const int q = lane >> 4, col = lane & 15;
     f32x4 bv[kCPW];
 #pragma unroll
@@ -140,7 +113,7 @@ __device__ __forceinline__ void conv(const uint8_t *smem, int in, const uint4 *_
     }
     const uint4 *wl = w + (size_t)(kCPW * wave) * kFrag + lane;
     constexpr int KS = TAPS * CB;
-    constexpr int DB = (CB % SPAI_CHESS_DB == 0) ? SPAI_CHESS_DB : 2;
+    constexpr int DB = (CB % kDB == 0) ? kDB : 2;
     uint4 A[DA][kCPW], B[DB > 2 ? DB : 2][NT];
     int rowoff[NT];
     auto geo = [&](int tap) {
@@ -176,7 +149,7 @@ __device__ __forceinline__ void conv(const uint8_t *smem, int in, const uint4 *_
         // taps as a runtime loop, channel blocks unrolled: ring slots stay static
 #pragma unroll
         for (int k = 0; k < DB - 1; ++k) load_b(k, B[k]);
-#pragma unroll SPAI_CHESS_TAP_UNROLL
+#pragma unroll kTapUnroll
         for (int tap = 0; tap < TAPS; ++tap) {
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) {
@@ -189,28 +162,15 @@ __device__ __forceinline__ void conv(const uint8_t *smem, int in, const uint4 *_
                     if (kb == CB) geo(tap + 1);   // every fetch of this tap is already issued
                     load_b(kb - CB, B[kb % DB]);
                 }
-#if SPAI_CHESS_PIN
                 // keep the prefetches here: the scheduler would otherwise sink them
                 // next to their MFMAs and expose the full L2 latency every k-step
                 __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
                 for (int c = 0; c < kCPW; ++c)
 #pragma unroll
                     for (int t = 0; t < NT; ++t)
                         acc[c][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(A[cb % DA][c]),
                                                                             as_bf16x8(B[cb % DB][t]), acc[c][t], 0, 0, 0);
-#if SPAI_CHESS_SCHED
-                // issue order: each MFMA followed by up to one LDS read, one weight load, two VALU
-#pragma unroll
-                for (int i = 0; i < kCPW * 8; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (i < 8) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    if (i < 4) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#endif
             }
         }
     } else {
@@ -230,13 +190,10 @@ __device__ __forceinline__ void conv(const uint8_t *smem, int in, const uint4 *_
                                                                         as_bf16x8(B[ks & 1][t]), acc[c][t], 0, 0, 0);
         }
     }
-#ifdef SPAI_CHESS_PREFETCH
-    if (wnext && pf == 0x9E3779B9u && acc[0][0][0] == -1234.5678f) sink[lane] = (float)pf;   // never taken
-#endif
 }
 
-// relu(acc [+ residual at OUT]) -> bf16 at OUT (in place over the residual)
-template <bool RES, int NT>
+// relu(acc) -> bf16 at OUT
+template <int NT>
 __device__ __forceinline__ void epilogue(uint8_t *smem, int out, int wave, int lane, const f32x4 (&acc)[kCPW][NT]) {
     const int q = lane >> 4, col = lane & 15;
 #pragma unroll
@@ -246,14 +203,7 @@ __device__ __forceinline__ void epilogue(uint8_t *smem, int out, int wave, int l
             const int v = (t >> 2) * 64 + (t & 3) * 16 + col;
             const int chunk = (kCPW * wave + c) * 2 + (q >> 1);
             uint2 *p = (uint2 *)(smem + out + row_chunk(v, chunk) + (q & 1) * 8);
-            f32x4 a = acc[c][t];
-            if (RES) {
-                const uint2 r = *p;
-                a[0] += bf_lo(r.x);
-                a[1] += bf_hi(r.x);
-                a[2] += bf_lo(r.y);
-                a[3] += bf_hi(r.y);
-            }
+            const f32x4 a = acc[c][t];
             *p = make_uint2(pack_relu_bf16x2(a[0], a[1]), pack_relu_bf16x2(a[2], a[3]));
         }
 }
@@ -264,9 +214,6 @@ __device__ __forceinline__ void epilogue(uint8_t *smem, int out, int wave, int l
 // tile's 16 channels.  One exact product plus zeros and a single fp32 rounding:
 // the value of the VALU add it replaces.  Wave w owns co tiles 4w..4w+3, i.e.
 // whole 32-channel blocks, so no other wave writes them meanwhile.
-#ifndef SPAI_CHESS_RES_MFMA
-#define SPAI_CHESS_RES_MFMA 1
-#endif
 template <int NT>
 __device__ __forceinline__ void residual_mfma(const uint8_t *smem, int out, int wave, int lane,
                                               f32x4 (&acc)[kCPW][NT]) {
@@ -323,31 +270,22 @@ __device__ __forceinline__ void forward_body(uint8_t *smem, uint32_t count, uint
     __syncthreads();
     f32x4 acc[kCPW][NT];
     conv<9, 1, NT>(smem, kBufB, W.w_stem, W.b_stem, wave, lane, acc);
-    epilogue<false, NT>(smem, kBufA, wave, lane, acc);
+    epilogue<NT>(smem, kBufA, wave, lane, acc);
     __syncthreads();
     for (int l = 0; l < W.blocks; ++l) {
-#ifdef SPAI_CHESS_EXP_FIXW   // timing experiment (wrong results): every block reads block 0's weights (L2-resident)
-        const size_t l1 = 0, l2 = 1;
-#else
         const size_t l1 = 2 * l, l2 = 2 * l + 1;
-#endif
-        conv<9, 8, NT>(smem, kBufA, W.w_res + l1 * 72 * kCT * kFrag, W.b_res + l1 * kHid, wave, lane, acc,
-                       W.w_res + l2 * 72 * kCT * kFrag, value);
-        epilogue<false, NT>(smem, kBufB, wave, lane, acc);
+        conv<9, 8, NT>(smem, kBufA, W.w_res + l1 * 72 * kCT * kFrag, W.b_res + l1 * kHid, wave, lane, acc);
+        epilogue<NT>(smem, kBufB, wave, lane, acc);
         __syncthreads();
         conv<9, 8, NT>(smem, kBufB, W.w_res + l2 * 72 * kCT * kFrag, W.b_res + l2 * kHid, wave, lane, acc,
-                       l + 1 < W.blocks ? W.w_res + (l2 + 1) * 72 * kCT * kFrag : nullptr, value);
-        if (SPAI_CHESS_RES_MFMA) {
-            residual_mfma<NT>(smem, kBufA, wave, lane, acc);
-            epilogue<false, NT>(smem, kBufA, wave, lane, acc);
-        } else {
-            epilogue<true, NT>(smem, kBufA, wave, lane, acc);
-        }
+                       l + 1 < W.blocks ? W.w_res + (l2 + 1) * 72 * kCT * kFrag : nullptr);
+        residual_mfma<NT>(smem, kBufA, wave, lane, acc);
+        epilogue<NT>(smem, kBufA, wave, lane, acc);
         __syncthreads();
     }
     // ---- policy head: conv1x1 256->256 + ReLU -> buffer B
     conv<1, 8, NT>(smem, kBufA, W.w_p1, W.b_p1, wave, lane, acc);
-    epilogue<false, NT>(smem, kBufB, wave, lane, acc);
+    epilogue<NT>(smem, kBufB, wave, lane, acc);
     // ---- value head (VALU, fp32): conv1x1 256->1 + ReLU per cell, from buffer A
     __syncthreads();
     {

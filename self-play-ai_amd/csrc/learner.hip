@@ -622,121 +622,14 @@ __global__ __launch_bounds__(kThreads) void k_conv_mfma(const float *__restrict_
     }
 }
 
-// k_conv_mfma<CINP, 1> (plain: no BatchNorm work) for SPW samples per workgroup:
-// workgroup (sample pair, 16-channel slice), the K split over the 4 waves as
-// there.  A wave's weight registers (its K part of the slice) serve every sample,
-// so a workgroup loads them once for SPW samples, and each k-step issues 3 SPW
-// MFMAs on one weight operand.  Samples past nsamp (odd batch) compute on a copy
-// of the last sample and store nothing.
-template <int CINP, int SPW>
-__global__ __launch_bounds__(kThreads) void k_conv_mfma_spw(const float *__restrict__ in, int cin,
-                                                            const float *__restrict__ wk,
-                                                            const float *__restrict__ bias, int cout, int coutp_all,
-                                                            float *__restrict__ out, int accumulate, int nsamp) {
-    constexpr int KS = 4, CSN = CINP / 4, KSTEPS = 9 * CSN, PER = KSTEPS / KS, MTS = 3;
-    static_assert(KSTEPS % KS == 0, "4 whole K parts");
-    extern __shared__ float sm[];
-    float *red = sm + SPW * CINP * kPlane;   // K-split partials [3 parts][SPW][3 mt][64 lanes][4]
-    const int lane = threadIdx.x & 63, part = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int s0 = part * PER, row = lane & 15, kq = lane >> 4;
-    const int co0 = 16 * (int)blockIdx.y;
-    const float *wl = wk + (size_t)(4 * s0 + kq) * coutp_all + co0 + row;
-    float bq[PER];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) bq[i] = wl[(size_t)i * 4 * coutp_all];
-    int bs[SPW];
-#pragma unroll
-    for (int s = 0; s < SPW; ++s) {
-        const int b = (int)blockIdx.x * SPW + s;
-        bs[s] = b < nsamp ? b : nsamp - 1;
-        stage_planes_fast<CINP>(in + (size_t)bs[s] * cin * kCells, cin, sm + s * CINP * kPlane);
-    }
-    __syncthreads();
-    const float *xb[SPW][MTS];
-#pragma unroll
-    for (int s = 0; s < SPW; ++s)
-#pragma unroll
-        for (int mt = 0; mt < MTS; ++mt) {
-            const int p = mt * 16 + row, pp = p < kCells ? p : 0;
-            xb[s][mt] = sm + s * CINP * kPlane + kq * kPlane + (pp / kCols + 1) * 9 + pp % kCols + 1 - 10;
-        }
-    f32x4 acc[SPW][MTS];
-#pragma unroll
-    for (int s = 0; s < SPW; ++s)
-#pragma unroll
-        for (int mt = 0; mt < MTS; ++mt) acc[s][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto kloop = [&](auto part_c) {
-        constexpr int s0c = decltype(part_c)::value * PER;
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int k = s0c + i, tap = k / CSN, cs = k % CSN;
-            const int off = 4 * cs * kPlane + tap_off(tap) + 10;
-#pragma unroll
-            for (int s = 0; s < SPW; ++s)
-#pragma unroll
-                for (int mt = 0; mt < MTS; ++mt)
-                    acc[s][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[s][mt][off], bq[i], acc[s][mt], 0, 0, 0);
-        }
-    };
-    if (part == 0) kloop(std::integral_constant<int, 0>{});
-    else if (part == 1) kloop(std::integral_constant<int, 1>{});
-    else if (part == 2) kloop(std::integral_constant<int, 2>{});
-    else kloop(std::integral_constant<int, 3>{});
-    if (part > 0) {
-        float *dst = red + ((size_t)(part - 1) * SPW * MTS * 64 + lane) * 4;
-#pragma unroll
-        for (int s = 0; s < SPW; ++s)
-#pragma unroll
-            for (int mt = 0; mt < MTS; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) dst[(s * MTS + mt) * 64 * 4 + r] = acc[s][mt][r];
-    }
-    __syncthreads();
-    if (part > 0) return;   // no barrier follows
-#pragma unroll
-    for (int q = 1; q < KS; ++q) {   // the fixed order of k_conv_mfma's sum
-        const float *src = red + ((size_t)(q - 1) * SPW * MTS * 64 + lane) * 4;
-#pragma unroll
-        for (int s = 0; s < SPW; ++s)
-#pragma unroll
-            for (int mt = 0; mt < MTS; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[s][mt][r] += src[(s * MTS + mt) * 64 * 4 + r];
-    }
-    const int n = co0 + row;
-    if (n >= cout) return;
-    const float bv = bias ? bias[n] : 0.f;
-#pragma unroll
-    for (int s = 0; s < SPW; ++s) {
-        if ((int)blockIdx.x * SPW + s >= nsamp) continue;
-        float *ob = out + ((size_t)bs[s] * cout + n) * kCells;
-#pragma unroll
-        for (int mt = 0; mt < MTS; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int p = mt * 16 + 4 * kq + r;
-                if (p < kCells) {
-                    const float v = acc[s][mt][r] + bv;
-                    ob[p] = accumulate ? ob[p] + v : v;
-                }
-            }
-    }
-}
-
 // weight-gradient partials: workgroup (chunk, group) accumulates, over the
 // kWgSamples samples of its chunk, the output tiles of its tile group:
 //   part[chunk][n][k] = sum_{b in chunk} sum_p dz[b][n][p] * X[b][p][k]   (k tap-major over CINP)
 // (the conv bias gradient, sum dz, comes out of the BN backward, k_bn_bwd)
 // GEMM rows = output channels (coutp/16 tiles), columns = k (round16(9 CINP)/16
 // tiles), reduction = each sample's 42 positions (11 k-steps of 4).
-#ifndef SPAI_WG_SAMPLES
-#define SPAI_WG_SAMPLES 4
-#endif
-constexpr int kWgSamples = SPAI_WG_SAMPLES;
-#ifndef SPAI_WG_TILES
-#define SPAI_WG_TILES 3
-#endif
-constexpr int kWgMaxTiles = SPAI_WG_TILES;   // tiles per wave (144 tiles / 12 groups / 4 waves at 64 x 64: 384 workgroups at B = 128)
+constexpr int kWgSamples = 4;
+constexpr int kWgMaxTiles = 3;   // tiles per wave (144 tiles / 12 groups / 4 waves at 64 x 64: 384 workgroups at B = 128)
 // BIAS: one more GEMM column k = K over a plane of ones, part[..][n][K] = sum_p dz:
 // the conv bias gradient (for the layers whose BN backward runs in the data
 // gradient's staging, kBnGrad)
@@ -844,13 +737,7 @@ __global__ __launch_bounds__(kThreads) void k_wgrad_mfma(const float *__restrict
 // dW[n][c][tap] = sum_chunk part[chunk][n][tap * cinp + c]  (fixed order).  At
 // batch 128 there are 32 chunks: all 32 loads in flight at once, and 64-thread
 // workgroups (576 of them for 64 x 64, instead of 144 of 256 threads on 256 CUs)
-#ifndef SPAI_WG_REDUCE_BATCH
-#define SPAI_WG_REDUCE_BATCH 32
-#endif
-#ifndef SPAI_WG_REDUCE_THREADS
-#define SPAI_WG_REDUCE_THREADS 64
-#endif
-constexpr int kWgReduceBatch = SPAI_WG_REDUCE_BATCH, kWgReduceThreads = SPAI_WG_REDUCE_THREADS;
+constexpr int kWgReduceBatch = 32, kWgReduceThreads = 64;
 __global__ void k_wgrad_reduce(const float *__restrict__ part, int B, int cin, int cout, float *__restrict__ dw,
                                float *__restrict__ dbias) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1218,37 +1105,17 @@ int learner_alloc_batch(spai_learner *L, uint32_t B) {
 // its own workgroup with the K split over its 4 waves (grid B x coutp/16: 4x
 // the workgroups of one per sample); the stem's input (4 padded channels, 9
 // k-steps) keeps one workgroup per sample with a wave per channel tile.
-// samples per workgroup of the plain convs (1: k_conv_mfma; 2: k_conv_mfma_spw, a
-// measured variant: 12.7 against 10.9 us per conv, 181k against 189k samples/s --
-// its 272 registers leave one workgroup per CU, whose staging, k-loop and K-part
-// sum then run back to back instead of overlapping another workgroup's;
-// profiles/r05/learner/spw)
-#ifndef SPAI_CONV_SPW
-#define SPAI_CONV_SPW 1
-#endif
-constexpr int kConvSpw = SPAI_CONV_SPW;
+// (Two samples per workgroup on one set of weight registers was measured slower:
+// 12.7 against 10.9 us per conv, 181k against 189k samples/s -- its 272 registers
+// leave one workgroup per CU, whose staging, k-loop and K-part sum then run back to
+// back instead of overlapping another workgroup's; profiles/r05/learner/spw.)
 
 template <int CINP, int MODE>
 int launch_conv_t(int B, size_t lds, hipStream_t st, const float *in, int cin, const float *wk, const float *bias,
                   int cout, float *out, int acc, const BnIn &bn, const BnIn &bo, const BnGrad &bg, const GradStats &gs) {
     constexpr int ks = 9 * CINP / 4;
     const int nt = round16(cout) / 16;
-#ifdef SPAI_SLICE_NT2   // variant: 32-channel slices, the K split over 2 wave pairs
-    if constexpr (ks % 2 == 0) {
-        if (nt % 2 == 0) {
-            k_conv_mfma<CINP, 2, MODE><<<dim3(B, nt / 2), kThreads, lds, st>>>(in, cin, wk, bias, cout, 16 * nt, out,
-                                                                              acc, bn, bo, bg, gs);
-            return SPAI_OK;
-        }
-    }
-#endif
     if constexpr (ks % 4 == 0) {
-        if constexpr (MODE == 0 && kConvSpw > 1) {   // plain conv: kConvSpw samples per workgroup
-            const size_t lds2 = ((size_t)kConvSpw * CINP * kPlane + (size_t)3 * kConvSpw * 3 * 64 * 4) * sizeof(float);
-            k_conv_mfma_spw<CINP, kConvSpw><<<dim3((B + kConvSpw - 1) / kConvSpw, nt), kThreads, lds2, st>>>(
-                in, cin, wk, bias, cout, 16 * nt, out, acc, B);
-            return SPAI_OK;
-        }
         k_conv_mfma<CINP, 1, MODE><<<dim3(B, nt), kThreads, lds, st>>>(in, cin, wk, bias, cout, 16 * nt, out, acc, bn,
                                                                       bo, bg, gs);
         return SPAI_OK;
@@ -1453,7 +1320,6 @@ void learner_destroy(spai_learner *L) {
     if (L->eng) (void)hipStreamSynchronize(L->eng->stream);
     for (hipStream_t ws : L->wg_stream)
         if (ws) (void)hipStreamSynchronize(ws);
-    if (L->graph) (void)hipGraphExecDestroy(L->graph);
     if (L->comm) (void)ncclCommDestroy((ncclComm_t)L->comm);
     for (hipEvent_t ev : L->ev_dz)
         if (ev) (void)hipEventDestroy(ev);
@@ -1602,16 +1468,14 @@ int enqueue_step(spai_learner *L, uint32_t B, hipStream_t st, const float *x_in,
                                                                              32 * kCells, L->d1.p);
     // conv l's dz (written over z[l] by k_bn_bwd) feeds its data gradient here and
     // its weight gradient on a side stream; nothing rewrites z[l] before the next step
-#ifndef SPAI_WG_SIDE
-#define SPAI_WG_SIDE spai_learner::kWgStreams
-#endif
+    constexpr int kWgSide = spai_learner::kWgStreams;   // side streams the weight gradients rotate over
     int side = 0;
     // dz: the layer's BN-backward output (z[l] overwritten by k_bn_bwd, or the fused
     // path's dz buffer); db: the bias gradient from the weight gradient (fused path)
     auto wgrad_async = [&](int l, const float *in, const float *dz = nullptr, float *db = nullptr) {
         const spai_learner::Conv &c = L->convs[l];
         if (crc != SPAI_OK) return;
-        const int k = side++ % SPAI_WG_SIDE;
+        const int k = side++ % kWgSide;
         if (hipEventRecord(L->ev_dz[l], st) != hipSuccess ||
             hipStreamWaitEvent(L->wg_stream[k], L->ev_dz[l], 0) != hipSuccess) {
             set_error("learner: event record/wait failed");
@@ -1709,7 +1573,7 @@ int enqueue_step(spai_learner *L, uint32_t B, hipStream_t st, const float *x_in,
     bn_conv_bwd(0, L->d0.p, x_in, nullptr, false, nullptr);
     }
     // join: every weight gradient is in G before the reduction and Adam
-    for (int k = 0; k < SPAI_WG_SIDE && crc == SPAI_OK; ++k)
+    for (int k = 0; k < kWgSide && crc == SPAI_OK; ++k)
         if (hipEventRecord(L->ev_wg_done[k], L->wg_stream[k]) != hipSuccess ||
             hipStreamWaitEvent(st, L->ev_wg_done[k], 0) != hipSuccess) {
             set_error("learner: event record/wait failed");
@@ -1742,7 +1606,7 @@ int enqueue_step(spai_learner *L, uint32_t B, hipStream_t st, const float *x_in,
 }
 
 // one step's batch and Adam bias corrections into the pinned staging half `stage`,
-// one DMA of it, the step (eager, or the captured graph); launch-only
+// one DMA of it, the step; launch-only
 static int stage_and_enqueue(spai_learner *L, uint32_t B, const float *states, const float *policies,
                              const float *values, float *stage) {
     hipStream_t st = L->eng->stream;
@@ -1757,37 +1621,10 @@ static int stage_and_enqueue(spai_learner *L, uint32_t B, const float *states, c
     SPAI_HIP(hipMemcpyAsync(L->batch_in.p, stage, (nin + 2) * 4, hipMemcpyHostToDevice, st));
     const float *x_in = L->batch_in.p, *pi_in = x_in + (size_t)B * 3 * kCells, *z_in = pi_in + (size_t)B * 7;
     const float *bc = L->batch_in.p + nin;
-    // SPAI_LEARNER_GRAPH=1 (measured variant): the step's launches captured once per
-    // batch size into a hipGraph and replayed (single-rank learners only: the host
-    // collective syncs inside the step).  Slower: the replay runs every kernel on one
-    // queue, so the weight gradients lose their overlap with the data-gradient chain
-    // (profiles/r05/learner/graph; round 2 likewise, profiles/r02/learner/graph_ab.txt)
-    static const bool use_graph = [] {
-        const char *v = std::getenv("SPAI_LEARNER_GRAPH");
-        return v && std::atoi(v) != 0;
-    }();
-    if (use_graph && !L->comm && !L->host_ar) {
-        if (!L->graph || L->graph_batch != B) {
-            if (L->graph) (void)hipGraphExecDestroy(L->graph);
-            L->graph = nullptr;
-            hipGraph_t g = nullptr;
-            SPAI_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            const int rc = enqueue_step(L, B, st, x_in, pi_in, z_in, bc);
-            const hipError_t ec = hipStreamEndCapture(st, &g);
-            if (rc != SPAI_OK || ec != hipSuccess) {   // a failed capture: free the partial graph before returning
-                if (g) (void)hipGraphDestroy(g);
-                SPAI_TRY(rc);
-            }
-            SPAI_CHECK(ec == hipSuccess && g, SPAI_ERR_DEVICE, "learner: step capture failed (%s)", hipGetErrorString(ec));
-            const hipError_t ei = hipGraphInstantiate(&L->graph, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            SPAI_CHECK(ei == hipSuccess, SPAI_ERR_DEVICE, "learner: graph instantiation failed (%s)", hipGetErrorString(ei));
-            L->graph_batch = B;
-        }
-        SPAI_HIP(hipGraphLaunch(L->graph, st));
-    } else {
-        SPAI_TRY(enqueue_step(L, B, st, x_in, pi_in, z_in, bc));
-    }
+    // (Replaying the step as a captured hipGraph was measured slower twice: the replay
+    // runs every kernel on one queue, so the weight gradients lose their overlap with the
+    // data-gradient chain; profiles/r05/learner/graph, profiles/r02/learner/graph_ab.txt)
+    SPAI_TRY(enqueue_step(L, B, st, x_in, pi_in, z_in, bc));
     L->last_batch = B;
     return SPAI_OK;
 }

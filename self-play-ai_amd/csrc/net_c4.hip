@@ -51,13 +51,7 @@ constexpr int kWaves = 4;                  // plan waves: the work split of ever
 // each), exchange half their partial sums through LDS and each finishes half
 // the tasks; the stem, head and linear run on waves 0-3.  Group sizes <= 5 only
 // (the partial-sum buffer must fit beside the activations).
-#ifdef SPAI_W8
-constexpr int kPhysWaves = 8;
-#else
-constexpr int kPhysWaves = 4;
-#endif
-constexpr int kThreads = kPhysWaves * 64;
-constexpr int kStemThreads = kWaves * 64;   // the per-position setup work (stem weights, planes)
+constexpr int kThreads = kWaves * 64;
 constexpr int kKStepsRes = 18;             // 576 / 32
 constexpr int kHeadC = 35;                 // 32 policy + 3 value channels
 constexpr int kPolIn = 32 * c4::kCells;    // 1344
@@ -91,7 +85,7 @@ constexpr int kL = kB + kS * 16;           // linear partials [4 waves][halves][
 constexpr int kMaxBlocks = 20;
 constexpr int kBiasFloats = kHid + 2 * kMaxBlocks * kHid + kHid;   // stem, residual convs, head (64 padded)
 constexpr int kBias = kL + kWaves * kLinHalves * 64 * 4; // all conv biases, staged once per workgroup
-constexpr int kBiasPer = (kBiasFloats + kStemThreads - 1) / kStemThreads;   // per thread
+constexpr int kBiasPer = (kBiasFloats + kThreads - 1) / kThreads;   // per thread
 constexpr int kPlanes = kBias + kBiasFloats * 4;   // stem neighbour planes [8][34] u64 (272-B rows: positions
                                                    // in different 16-B bank groups)
 constexpr int kPlaneRow = 34;
@@ -103,15 +97,7 @@ constexpr int kTabRows = 128;                      // rows of a row table (8 til
 // registers at the head conv's start (an LDS-DMA copy made the compiler wait
 // vmcnt(0) at the head k-loop's first weight use).
 constexpr int kLinWPer = kLinBSteps / kWaves;      // B fragments per wave
-#ifdef SPAI_W8
-constexpr int kSRun = 5;                   // largest group size this build runs
-constexpr int kSplitMaxN = 14;             // most tasks of a plan wave at S <= kSRun (S = 5, position-major)
-constexpr int kPart = kTab + 42 * 16;      // split-K partial sums [4 plan waves][kSplitMaxN][64 lanes] x 16 B
-constexpr int kLdsBytes = kPart + kWaves * kSplitMaxN * 1024;
-#else
-constexpr int kSRun = kS;
 constexpr int kLdsBytes = kTab + 42 * 16;
-#endif
 #ifdef SPAI_DIAG_KSTEP
 constexpr int kStamps = 48;                // + 24..41: after each k-step of block 1 conv 1, 42 before its barrier, 43
                                            // after it, 44 at its start (diagnostic k-step build)
@@ -265,11 +251,11 @@ __host__ __device__ constexpr int first_kstep(int S, int t) {
 //    other orders run out of registers): wave W owns tasks [TT*W/4, TT*(W+1)/4)
 //    of task = pos_tile*CT + co_tile: ~NPT/4 position tiles, every co tile, so
 //    each wave streams all CT weight fragments per k-step;
-//  * co-major (NPT <= SPAI_CO_MAJOR_MAX_NPT): in the 64-channel layers wave W
+//  * co-major (NPT <= kCoMajorMaxNPT): in the 64-channel layers wave W
 //    owns co tile W over all NPT position tiles, so the CU fetches each weight
 //    fragment once per k-step (4 KiB) at NPT LDS reads per wave; in the head
 //    (CT = 3) a wave's contiguous task range spans at most 2 co tiles;
-//  * pair split (64-channel layers, NPT <= SPAI_PAIR_MAX_NPT): wave (j = W>>1, h = W&1) owns co
+//  * pair split (64-channel layers, NPT <= kPairMaxNPT): wave (j = W>>1, h = W&1) owns co
 //    tiles {2j, 2j+1} over position tiles [h*m, h*m+m) (m = NPT/2) plus, for
 //    odd NPT, the last tile in co tile 2j+h: NPT tasks per wave, 2 weight
 //    fragments per wave and k-step (8 KiB per CU), ~NPT/2 LDS reads.
@@ -277,37 +263,18 @@ __host__ __device__ constexpr int first_kstep(int S, int t) {
 // path delivers ~64 B/clk/CU, i.e. 16 KiB per k-step costs ~256 cycles.
 // Position tiles are addressed through a local index t < NT; gpt(t) is the
 // group's position tile, pt(i) the local tile and co(i) the co tile of task i.
-#ifndef SPAI_CO_MAJOR_MAX_NPT
-#define SPAI_CO_MAJOR_MAX_NPT 8
-#endif
-#ifndef SPAI_PAIR_MAX_NPT
-#define SPAI_PAIR_MAX_NPT 11
-#endif
-#ifndef SPAI_HEAD_CO_MAJOR_MAX_NPT
-#define SPAI_HEAD_CO_MAJOR_MAX_NPT 8   // the head conv (CT = 3) in co-major order up to this many tiles
-#endif
-// Deferred epilogue (SPAI_DEFER_EPI).  A trunk conv's fused epilogue (ReLU, bf16 pack,
-// LDS store: 8 VALU + a store per task) cannot hide in the last tap's MFMA gaps (an
-// MFMA leaves 8 issue cycles free, a task's epilogue needs ~44), so at the
-// position-major group sizes (S >= 5) the tasks of co tiles 2 and 3 -- output
-// channels 32-63 -- keep their fp32 accumulators into the NEXT layer, which runs the
-// K-half-0 k-steps of every tap (input channels 0-31) first and does those deferred
-// epilogues in their MFMA gaps; a barrier then publishes channels 32-63 before the
-// K-half-1 k-steps read them.  The K order is the same at every group size (the sums,
-// and so the results, do not depend on S).
-#ifdef SPAI_DEFER_EPI
-constexpr bool kDefer = true;
-#else
-constexpr bool kDefer = false;
-#endif
-// k-step executed j-th in a layer (k = tap * 2 + K half)
-__host__ __device__ constexpr int kstep_of(int j) { return kDefer ? (j < 9 ? 2 * j : 2 * (j - 9) + 1) : j; }
+constexpr int kCoMajorMaxNPT = 8;       // 64-channel layers in co-major order up to this many tiles
+constexpr int kPairMaxNPT = 11;         // ... and as a pair split up to this many
+constexpr int kHeadCoMajorMaxNPT = 8;   // the head conv (CT = 3) in co-major order up to this many tiles
+// (A deferred epilogue -- the tasks of output channels 32-63 keeping their fp32
+// accumulators into the next layer, which packs and stores them in the MFMA gaps of its
+// first k-steps -- was measured slower and is retired)
 
 template <int W, int CT, int NPT>
 struct Plan {
-    static constexpr int MODE = NPT <= (CT == 3 ? SPAI_HEAD_CO_MAJOR_MAX_NPT : SPAI_CO_MAJOR_MAX_NPT) ? 1
-                                : CT == 4 && NPT <= SPAI_PAIR_MAX_NPT                              ? 2
-                                                                                                    : 0;
+    static constexpr int MODE = NPT <= (CT == 3 ? kHeadCoMajorMaxNPT : kCoMajorMaxNPT) ? 1
+                                : CT == 4 && NPT <= kPairMaxNPT                          ? 2
+                                                                                          : 0;
     static constexpr int TT = NPT * CT;
     // position-major / co-major: a contiguous task range
     static constexpr int first = TT * W / 4;
@@ -331,19 +298,6 @@ struct Plan {
         return MODE == 2 ? (i < 2 * m ? 2 * pj + (i & 1) : 2 * pj + ph)
                          : MODE == 1 ? (first + i) / NPT : (first + i) % CT;
     }
-    // deferred epilogue: the position-major 64-channel plans defer their co-tile 2/3 tasks
-    static constexpr bool DEFER = kDefer && CT == 4 && MODE == 0;
-    static constexpr int count_deferred() {
-        int c = 0;
-        for (int i = 0; i < n; ++i) c += co(i) >= 2;
-        return c;
-    }
-    static constexpr int ND = DEFER ? count_deferred() : 0;
-    // the deferred accumulators are indexed by task (dacc[i], only the deferred ones live):
-    // every index stays a plain expression of the unrolled loop counters, so the arrays are
-    // scalarised into registers (a loop-valued task map left them on the scratch stack)
-    static constexpr int NDA = ND > 0 ? n : 1;
-    static constexpr bool deferred(int i) { return DEFER && co(i) >= 2; }
 };
 
 // Per-lane LDS geometry, computed once per kernel (positions are the same for
@@ -461,10 +415,7 @@ __device__ __forceinline__ void make_geo(const uint8_t *smem, int lane, Geo<Plan
 // (S, W, t) of the 64-channel layers' plan (the head conv runs on it too) holds
 // 64 lanes x 32 B: {rel2[5], epi, aux, 0}; aux = s | (bit col*7+row) << 8 for the
 // stem and the head-feature offsets (padding rows: s = S, a zeroed plane row).
-#ifndef SPAI_GEO_NT
-#define SPAI_GEO_NT 8
-#endif
-constexpr int kGeoNT = SPAI_GEO_NT;   // the most position tiles a wave holds (S = 3, co-major; 11 for a pair split at S = 8)
+constexpr int kGeoNT = 8;   // the most position tiles a wave holds (S = 3, co-major; 11 for a pair split at S = 8)
 __host__ __device__ constexpr size_t lane_geo_at(int S, int W, int t) {
     return (((size_t)(S - 1) * kWaves + W) * kGeoNT + t) * 64 * 2;   // in uint4
 }
@@ -539,39 +490,16 @@ __global__ __launch_bounds__(64) void k_geo_init(const uint4 *__restrict__ geo, 
 // hide a weight load (L2) or an LDS read behind, but registers to spare.
 // (DA must divide the 18 k-steps of a layer: the ring carries the next layer's
 // first DA-1 k-steps in the slots a fresh layer expects.)
-// scheduling of an ordinary k-step (knobs, round 6): the MFMA / VALU / LDS / VMEM
-// interleave hints, and the scheduling fence that closes each k-step
-// the fused last tap's per-task hints and fence (final_tap_epilogue; knobs)
-#ifndef SPAI_FINAL_HINTS
-#define SPAI_FINAL_HINTS 1
-#endif
-#ifndef SPAI_FINAL_FENCE
-#define SPAI_FINAL_FENCE 1
-#endif
-#ifndef SPAI_ISSUE_HINTS
-#define SPAI_ISSUE_HINTS 0   // 1: the round-3 interleave hints (-2.5 % sims/s in round 6, profiles/r06/sched)
-#endif
-#ifndef SPAI_KSTEP_FENCE
-#define SPAI_KSTEP_FENCE 1
-#endif
-#ifndef SPAI_DA4
-#define SPAI_DA4 6   // A ring at S = 4 (tuning knob)
-#endif
-#ifndef SPAI_DB4
-#define SPAI_DB4 2   // B ring at S = 4 (tuning knob)
-#endif
-#ifndef SPAI_DA8
-#ifdef SPAI_FINAL2
-#define SPAI_DA8 6   // the two-tap final phase (final_phase2) holds k-steps 14-17 in four ring slots
-#else
-#define SPAI_DA8 3   // A ring at S >= 5 (tuning knob)
-#endif
-#endif
-#ifndef SPAI_DB8
-#define SPAI_DB8 3   // B ring at S >= 5 (tuning knob; 3 since round 6 without the issue hints: +0.5 %, profiles/r06/sched)
-#endif
-__host__ __device__ constexpr int a_depth(int S) { return S <= 2 ? 9 : S <= 3 ? 6 : S <= 4 ? SPAI_DA4 : SPAI_DA8; }
-__host__ __device__ constexpr int b_depth(int S) { return S <= 2 ? 4 : S <= 3 ? 3 : S <= 4 ? SPAI_DB4 : SPAI_DB8; }
+// Each ordinary k-step closes with a scheduling fence, and the fused last tap
+// (final_tap_epilogue) orders every task with interleave hints and a fence; the
+// round-3 interleave hints inside an ordinary k-step were -2.5 % sims/s in round 6
+// (profiles/r06/sched).
+constexpr int kDA4 = 6;   // A ring at S = 4
+constexpr int kDB4 = 2;   // B ring at S = 4
+constexpr int kDA8 = 3;   // A ring at S >= 5
+constexpr int kDB8 = 3;   // B ring at S >= 5 (3 since round 6 without the issue hints: +0.5 %, profiles/r06/sched)
+__host__ __device__ constexpr int a_depth(int S) { return S <= 2 ? 9 : S <= 3 ? 6 : S <= 4 ? kDA4 : kDA8; }
+__host__ __device__ constexpr int b_depth(int S) { return S <= 2 ? 4 : S <= 3 ? 3 : S <= 4 ? kDB4 : kDB8; }
 
 // implicit-GEMM 3x3 conv over the LDS activations at IN for wave W's tasks.
 // Software pipeline: A (weights, global/L2) DA-1 k-steps ahead, B (LDS) DB-1
@@ -584,31 +512,19 @@ __host__ __device__ constexpr int b_depth(int S) { return S <= 2 ? 4 : S <= 3 ? 
 // weights without a cold start.  `wn` is always a valid layer (the current one
 // when nothing follows): an unconditional prefetch keeps the vmcnt bookkeeping
 // free of branches.
-// Timing-only deletion experiments (diagnostic builds; wrong results):
-// SPAI_EXP_NOA replaces the k-loop's weight loads by a register value, SPAI_EXP_NOB
-// its activation reads, SPAI_EXP_NOBAR drops the barrier between trunk layers.
-__device__ __forceinline__ uint4 exp_a(const uint4 &src, int lane, int k) {
-#ifdef SPAI_EXP_NOA
-    (void)src;
-    return make_uint4(0x3F803F80u ^ (uint32_t)(lane + k), 0x3F803F80u, 0x3F803F80u, (uint32_t)k);
-#else
+
+// The k-loop's weight (global) and activation (LDS) fragment loads.  `lane` and `k` are
+// unused: they fed retired timing experiments that replaced a load by a register value.
+// They stay for now because k_forward's compiled bytes change when they go, and the
+// retirement kept every kernel's device code identical (profiles/variant_retirement).
+// Inline both with the next change that moves this kernel's code anyway.
+__device__ __forceinline__ uint4 frag_a(const uint4 &src, int lane, int k) {
     (void)lane, (void)k;
     return src;
-#endif
 }
-__device__ __forceinline__ uint4 exp_b(const uint8_t *p, int lane, int k) {
-#ifdef SPAI_EXP_NOB
-    (void)p;
-    return make_uint4(0x3F803F80u ^ (uint32_t)(lane * 3 + k), 0x3F803F80u, 0x3F803F80u, (uint32_t)k);
-#else
+__device__ __forceinline__ uint4 frag_b(const uint8_t *p, int lane, int k) {
     (void)lane, (void)k;
     return *(const uint4 *)p;
-#endif
-}
-__device__ __forceinline__ void layer_barrier() {
-#ifndef SPAI_EXP_NOBAR
-    __syncthreads();
-#endif
 }
 
 // The last tap of a 64-channel layer, task-major, with the epilogue fused
@@ -621,16 +537,9 @@ __device__ __forceinline__ void final_tap_epilogue(uint8_t *smem, const Geo<Plan
                                                    const uint4 (&B)[DB][Plan<W, CT, NPT>::NT],
                                                    const f32x4 (&bv)[Plan<W, CT, NPT>::CTL],
                                                    f32x4 (&acc)[Plan<W, CT, NPT>::n],
-                                                   const int (&hoff)[Plan<W, CT, NPT>::NT],
-                                                   f32x4 (&dacc)[Plan<W, CT, NPT>::NDA]) {
+                                                   const int (&hoff)[Plan<W, CT, NPT>::NT]) {
     using PL = Plan<W, CT, NPT>;
-    // (EPI 1/2 with a deferring plan: the co-tile 2/3 tasks hand their accumulators on instead)
-    auto defer = [](int i) { return EPI < 3 && PL::deferred(i); };
-#ifdef SPAI_EXP_EPI_LAG
-    constexpr int n = PL::n, k0 = kKStepsRes - 2, D = SPAI_EXP_EPI_LAG;   // timing experiment: epilogue lag
-#else
     constexpr int n = PL::n, k0 = kKStepsRes - 2, D = 2;
-#endif
     static_assert(CT == 4, "fused epilogue: 64-channel layers");
     auto live = [](int t, int ks) { return !((tap_skip(S, PL::gpt(t)) >> (ks >> 1)) & 1); };
     auto task_on = [](int i) { return !(EPI == 3 && PL::co(i) == 3); };   // the head has no co tile 3
@@ -666,10 +575,9 @@ __device__ __forceinline__ void final_tap_epilogue(uint8_t *smem, const Geo<Plan
             }
             const int t = PL::gpt(PL::pt(i)), c = PL::co(i) - PL::C0;
 #pragma unroll
-            for (int j = k0; j < kKStepsRes; ++j) {
-                const int ks = kstep_of(j);
+            for (int ks = k0; ks < kKStepsRes; ++ks) {
                 if (task_on(i) && live(PL::pt(i), ks)) {
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(A[j % DA][c]), as_bf16x8(B[j % DB][PL::pt(i)]),
+                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(A[ks % DA][c]), as_bf16x8(B[ks % DB][PL::pt(i)]),
                                                                     ks == first_kstep(S, t) ? bv[c] : acc[i], 0, 0, 0);
                     ++nm;
                 }
@@ -680,42 +588,12 @@ __device__ __forceinline__ void final_tap_epilogue(uint8_t *smem, const Geo<Plan
                 ++nm;
             }
         }
-        if (i >= D && EPI < 3 && !defer(i - D)) {
+        if (i >= D && EPI < 3) {
             const int j = i - D;
             const int off = OUT + (g.epi[PL::pt(j)] ^ (PL::co(j) << 5));
-#if defined(SPAI_EXP_NOEPI) || defined(SPAI_EXP_NOEPI_ALL)
-            // timing-only deletion experiments (wrong results): no conversion VALU (the accumulator
-            // kept alive in its AGPRs), zeros stored -- or (NOEPI_ALL) no store either
-            asm volatile("" ::"a"(acc[j]));
-#ifdef SPAI_EXP_NOEPI
-            *(uint2 *)(smem + off) = make_uint2(0u, (uint32_t)off);
-            nw = 1;
-#endif
-            nv = 0;
-#elif defined(SPAI_EXP_STORE_B128)
-            // timing-only experiment (wrong results): the same bytes as half as many 16-B
-            // stores (task pairs; the second task of a pair stores nothing)
-            if ((j & 1) == 0) {
-                const uint32_t a0 = pack_relu_bf16x2(acc[j][0], acc[j][1]), a1 = pack_relu_bf16x2(acc[j][2], acc[j][3]);
-                const int j2 = j + 1 < PL::n ? j + 1 : j;
-                const uint32_t b0 = pack_relu_bf16x2(acc[j2][0], acc[j2][1]), b1 = pack_relu_bf16x2(acc[j2][2], acc[j2][3]);
-                *(uint4 *)(smem + (off & ~15)) = make_uint4(a0, a1, b0, b1);
-                nw = 1;
-            }
-            nv = 5;
-#elif defined(SPAI_EXP_STORE_LIN)
-            // timing-only experiment (wrong results): the same stores at bank-conflict-free
-            // addresses (each 16-lane group writes 128 contiguous bytes)
-            (void)off;
-            *(uint2 *)(smem + OUT + j * 512 + lane * 8) = make_uint2(pack_relu_bf16x2(acc[j][0], acc[j][1]),
-                                                                     pack_relu_bf16x2(acc[j][2], acc[j][3]));
-            nv = 5;
-            nw = 1;
-#else
             *(uint2 *)(smem + off) = make_uint2(pack_relu_bf16x2(acc[j][0], acc[j][1]), pack_relu_bf16x2(acc[j][2], acc[j][3]));
             nv = 5;
             nw = 1;
-#endif
         } else if (EPI == 3 && i >= D && task_on(i - D)) {   // the head: H[s][cell * 36 + c] for the 35 real channels
             const int j = i - D, co0 = PL::co(j) * 16 + 4 * (lane >> 4), off = hoff[PL::pt(j)];
             // a lane with nothing to store writes its own word of the (not yet used) linear partials
@@ -725,7 +603,6 @@ __device__ __forceinline__ void final_tap_epilogue(uint8_t *smem, const Geo<Plan
             nw = 1;
         }
         // issue order: the MFMAs with the epilogue's 5 VALU in their gaps, then the store and the read
-#if SPAI_FINAL_HINTS
         if (nm >= 1) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             if (nv) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
@@ -745,118 +622,6 @@ __device__ __forceinline__ void final_tap_epilogue(uint8_t *smem, const Geo<Plan
         }
         if (nw) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
         if (nrd) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-#else
-        (void)nv;
-        (void)nw;
-        (void)nrd;
-#endif
-#if SPAI_FINAL_FENCE
-        __builtin_amdgcn_sched_barrier(0);
-#endif
-    }
-    if constexpr (EPI < 3 && PL::ND > 0) {
-#pragma unroll
-        for (int i = 0; i < PL::n; ++i)
-            if (PL::deferred(i)) dacc[i] = acc[i];
-    }
-}
-
-// SPAI_FINAL2: at the position-major group sizes (S >= 5) the last TWO taps (k-steps
-// 14-17) run task-major with the epilogue fused, so the LDS stores of the finished
-// tasks overlap twice as many MFMAs as in final_tap_epilogue (round 6: a trunk conv's
-// ~750 cycles of epilogue stores otherwise outlast its last tap, profiles/r06).  Each
-// task still adds its k-steps in order, so the results are those of the default.  The
-// B fragments of k-steps 14-17 are read per position tile, one tile ahead; the weights
-// of k-steps 14-17 sit in four distinct slots of the A ring (DA = 6).
-#ifdef SPAI_FINAL2
-constexpr bool kFinal2 = true;
-#else
-constexpr bool kFinal2 = false;
-#endif
-template <int W, int CT, int NPT, int S, int IN, int DA, int EPI, int OUT>
-__device__ __forceinline__ void final_phase2(uint8_t *smem, const Geo<Plan<W, CT, NPT>::NT> &g, int lane,
-                                             const uint4 (&A)[DA][Plan<W, CT, NPT>::CTL],
-                                             f32x4 (&acc)[Plan<W, CT, NPT>::n]) {
-    using PL = Plan<W, CT, NPT>;
-    constexpr int n = PL::n, NT = PL::NT, k0 = kKStepsRes - 4, D = 2;
-    static_assert(CT == 4 && PL::MODE == 0 && (EPI == 1 || EPI == 2), "final_phase2: position-major trunk convs");
-    static_assert(DA >= 6, "final_phase2: k-steps 14-17 need four distinct A slots");
-    auto live = [](int t, int ks) { return !((tap_skip(S, PL::gpt(t)) >> (ks >> 1)) & 1); };
-    uint4 Bf[2][4];   // k-steps 14-17 of one local tile, double-buffered over the tiles
-    auto read_tile = [&](int t) {
-        int nr = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int ks = k0 + k, tap = ks >> 1, flip = (ks & 1) << 6;
-            if (live(t, ks)) {
-                Bf[t & 1][k] = *(const uint4 *)(smem + (IN - 256) + (g.b(t, tap) ^ flip));
-                ++nr;
-            }
-        }
-        return nr;
-    };
-    uint4 id[2];   // the residual identities (final_tap_epilogue)
-    uint4 rb[3];   // residual B fragments, two tasks ahead
-    if (EPI == 2) {
-        const int m = lane & 15, q = lane >> 4;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int j = 16 * h + m - 8 * q;
-            uint32_t w[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w[e] = j == 2 * e ? 0x3F80u : j == 2 * e + 1 ? 0x3F800000u : 0u;
-            id[h] = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-#pragma unroll
-        for (int i = 0; i < 2 && i < n; ++i)
-            rb[i] = *(const uint4 *)(smem + (OUT - 256) + (g.b(PL::pt(i), 4) ^ ((PL::co(i) >> 1) << 6)));
-    }
-    read_tile(PL::pt(0));
-#pragma unroll
-    for (int i = 0; i < n + D; ++i) {
-        int nm = 0, nv = 0, nw = 0, nrd = 0;
-        if (i < n) {
-            const int t = PL::pt(i), c = PL::co(i) - PL::C0;
-            if ((i == 0 || PL::pt(i - 1) != t) && t + 1 < NT) nrd += read_tile(t + 1);   // the next tile, one tile ahead
-            if (EPI == 2 && i + 2 < n) {
-                rb[(i + 2) % 3] = *(const uint4 *)(smem + (OUT - 256) + (g.b(PL::pt(i + 2), 4) ^ ((PL::co(i + 2) >> 1) << 6)));
-                ++nrd;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (live(t, k0 + k)) {   // (the bias went in with the first live k-step, <= 8)
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(A[(k0 + k) % DA][c]),
-                                                                    as_bf16x8(Bf[t & 1][k]), acc[i], 0, 0, 0);
-                    ++nm;
-                }
-            if (EPI == 2) {
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(id[PL::co(i) & 1]), as_bf16x8(rb[i % 3]), acc[i],
-                                                                0, 0, 0);
-                ++nm;
-            }
-        }
-        if (i >= D) {
-            const int j = i - D;
-            const int off = OUT + (g.epi[PL::pt(j)] ^ (PL::co(j) << 5));
-            *(uint2 *)(smem + off) = make_uint2(pack_relu_bf16x2(acc[j][0], acc[j][1]), pack_relu_bf16x2(acc[j][2], acc[j][3]));
-            nv = 9;
-            nw = 1;
-        }
-        // issue order: each MFMA followed by 2 of the epilogue's VALU, then the rest, the
-        // store and the reads
-#pragma unroll
-        for (int k = 0; k < 5; ++k)
-            if (k < nm) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                if (nv) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-            }
-        if (nv && nm < 5) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-        if (nv && nm < 4) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-        if (nv && nm < 3) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-        if (nw) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-#pragma unroll
-        for (int k = 0; k < 5; ++k)
-            if (k < nrd) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -874,7 +639,6 @@ __device__ __forceinline__ void conv_mfma(uint8_t *smem, const Geo<Plan<W, CT, N
                                           uint4 (&A)[DA][Plan<W, CT, NPT>::CTL],
                                           f32x4 (&acc)[Plan<W, CT, NPT>::n],
                                           const int (&hoff)[Plan<W, CT, NPT>::NT],
-                                          f32x4 (&dacc)[Plan<W, CT, NPT>::NDA],
                                           unsigned long long *kst = nullptr) {
     using PL = Plan<W, CT, NPT>;
     constexpr int NT = PL::NT, CTL = PL::CTL;
@@ -903,7 +667,6 @@ __device__ __forceinline__ void conv_mfma(uint8_t *smem, const Geo<Plan<W, CT, N
         return on;
     };
     auto live = [&](int t, int ks) { return tile_on(t) && !((tap_skip(S, PL::gpt(t)) >> (ks >> 1)) & 1); };
-#ifndef SPAI_DEFER_EPI   // the k-loop in k-step order (production)
     uint4 B[DB][NT];
 #pragma unroll
     for (int kb = 0; kb < DB - 1; ++kb) {
@@ -918,31 +681,15 @@ __device__ __forceinline__ void conv_mfma(uint8_t *smem, const Geo<Plan<W, CT, N
         if (ks + la < kKStepsRes) {
 #pragma unroll
             for (int c = 0; c < CTL; ++c)
-                if (!(EPI == 3 && PL::C0 + c == 3)) A[(ks + la) % DA][c] = exp_a(wl[((ks + la) * CT + c) * 64], lane, ks + c);
+                if (!(EPI == 3 && PL::C0 + c == 3)) A[(ks + la) % DA][c] = frag_a(wl[((ks + la) * CT + c) * 64], lane, ks + c);
         } else if (EPI != 3) {   // (nothing follows the head)
 #pragma unroll
-            for (int c = 0; c < CTL; ++c) A[(ks + la) % DA][c] = exp_a(wnl[((ks + la - kKStepsRes) * CT + c) * 64], lane, ks + c);
+            for (int c = 0; c < CTL; ++c) A[(ks + la) % DA][c] = frag_a(wnl[((ks + la - kKStepsRes) * CT + c) * 64], lane, ks + c);
         }
     };
-    // k-steps in the task-major final phase: 4 with SPAI_FINAL2 at the position-major sizes
-    constexpr int KF = (EPI == 1 || EPI == 2) && kFinal2 && PL::MODE == 0 ? 4 : 2;
-    constexpr int kBEnd = KF == 2 ? kKStepsRes : kKStepsRes - KF;   // the ring's B reads end here
 #pragma unroll
     for (int ks = 0; ks < kKStepsRes; ++ks) {
-        if constexpr (KF == 4) if (ks == kKStepsRes - 4) {
-            // the next layer's second k-step's weights go to the slot k-step 13 left; the
-            // slots of k-steps 14-16 refill after the final phase
-            load_a(ks);
-            final_phase2<W, CT, NPT, S, IN, DA, EPI, OUT>(smem, g, lane, A, acc);
-            load_a(ks + 1);
-            load_a(ks + 2);
-            load_a(ks + 3);
-#ifdef SPAI_DIAG_KSTEP
-            if (kst) kst[ks] = __builtin_amdgcn_s_memtime();
-#endif
-            break;
-        }
-        if constexpr (EPI > 0 && KF == 2) if (ks == kKStepsRes - 2) {
+        if constexpr (EPI > 0) if (ks == kKStepsRes - 2) {
             // B reads of the last k-step (if not issued yet), then the fused final tap;
             // k-step 17's A prefetch waits for the MFMAs that read the slot it refills
             if (ks + lb < kKStepsRes) {
@@ -952,7 +699,7 @@ __device__ __forceinline__ void conv_mfma(uint8_t *smem, const Geo<Plan<W, CT, N
                     if (live(t, ks + lb)) B[(ks + lb) % DB][t] = *(const uint4 *)(smem + (IN - 256) + (g.b(t, tap) ^ flip));
             }
             load_a(ks);
-            final_tap_epilogue<W, CT, NPT, S, DA, DB, EPI, OUT>(smem, g, lane, A, B, bv, acc, hoff, dacc);
+            final_tap_epilogue<W, CT, NPT, S, DA, DB, EPI, OUT>(smem, g, lane, A, B, bv, acc, hoff);
             load_a(ks + 1);
 #ifdef SPAI_DIAG_KSTEP
             if (kst) kst[ks] = __builtin_amdgcn_s_memtime();
@@ -960,17 +707,12 @@ __device__ __forceinline__ void conv_mfma(uint8_t *smem, const Geo<Plan<W, CT, N
             break;
         }
         load_a(ks);
-        int nr = 0;   // B reads issued this k-step (for the issue-order hints)
-        if (ks + lb < kBEnd) {
+        if (ks + lb < kKStepsRes) {
             const int tap = (ks + lb) >> 1, flip = ((ks + lb) & 1) << 6;
 #pragma unroll
             for (int t = 0; t < NT; ++t)
-                if (live(t, ks + lb)) {
-                    B[(ks + lb) % DB][t] = exp_b(smem + (IN - 256) + (g.b(t, tap) ^ flip), lane, ks + t);
-                    ++nr;
-                }
+                if (live(t, ks + lb)) B[(ks + lb) % DB][t] = frag_b(smem + (IN - 256) + (g.b(t, tap) ^ flip), lane, ks + t);
         }
-        int nm = 0;
 #pragma unroll
         for (int i = 0; i < PL::n; ++i)
             if (task_on(i) && live(PL::pt(i), ks)) {
@@ -979,129 +721,12 @@ __device__ __forceinline__ void conv_mfma(uint8_t *smem, const Geo<Plan<W, CT, N
                                                                 as_bf16x8(B[ks % DB][PL::pt(i)]),
                                                                 ks == first_kstep(S, t) ? bv[PL::co(i) - PL::C0]
                                                                                         : acc[i], 0, 0, 0);
-                ++nm;
             }
-        // issue order for this k-step: each MFMA followed by up to 2 VALU, one
-        // LDS read (next B) and one weight load (A, DA-1 ahead)
-        const int ng = nm > nr ? nm : nr;
-#if SPAI_ISSUE_HINTS
-#pragma unroll
-        for (int i = 0; i < PL::n; ++i) {
-            if (i < ng) {
-                if (i < nm) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-                if (i < nr) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                if (i < CTL) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-        }
-#else
-        (void)ng;
-#endif
-#if SPAI_KSTEP_FENCE
-        __builtin_amdgcn_sched_barrier(0);
-#endif
+        __builtin_amdgcn_sched_barrier(0);   // the scheduling fence that closes each k-step
 #ifdef SPAI_DIAG_KSTEP
         if (kst) kst[ks] = __builtin_amdgcn_s_memtime();
 #endif
     }
-#else   // SPAI_DEFER_EPI: K-half-0 k-steps first, the previous layer's deferred epilogue in their gaps
-    uint4 B[DB][NT];
-    // B fragments of the j-th executed k-step (its tap and K half)
-    auto read_b = [&](int j) {
-        const int ks = kstep_of(j), tap = ks >> 1, flip = (ks & 1) << 6;
-        int nr = 0;
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-            if (live(t, ks)) {
-                B[j % DB][t] = exp_b(smem + (IN - 256) + (g.b(t, tap) ^ flip), lane, j + t);
-                ++nr;
-            }
-        return nr;
-    };
-#pragma unroll
-    for (int kb = 0; kb < DB - 1; ++kb) read_b(kb);
-    constexpr int la = DA - 1, lb = DB - 1;
-    // A for the k-step executed (j + la)-th (this layer's, or the next layer's first ones)
-    auto load_a = [&](int j) {
-        if (j + la < kKStepsRes) {
-            const int ks = kstep_of(j + la);
-#pragma unroll
-            for (int c = 0; c < CTL; ++c)
-                if (!(EPI == 3 && PL::C0 + c == 3)) A[(j + la) % DA][c] = exp_a(wl[(ks * CT + c) * 64], lane, j + c);
-        } else if (EPI != 3) {   // (nothing follows the head)
-            const int ks = kstep_of(j + la - kKStepsRes);
-#pragma unroll
-            for (int c = 0; c < CTL; ++c) A[(j + la) % DA][c] = exp_a(wnl[(ks * CT + c) * 64], lane, j + c);
-        }
-    };
-    // deferred epilogue of the previous layer (its co-tile 2/3 tasks, output channels
-    // 32-63 of IN) in the MFMA gaps of the K-half-0 k-steps; the barrier at the top of
-    // step jb publishes them before the first K-half-1 B reads (issued lb steps ahead)
-    constexpr int jb = 9 - lb;
-    constexpr bool din = PL::ND > 0;
-#pragma unroll
-    for (int j = 0; j < kKStepsRes; ++j) {
-        const int ks = kstep_of(j);
-        if constexpr (din) if (j == jb) __syncthreads();
-        if constexpr (EPI > 0) if (j == kKStepsRes - 2) {
-            // B reads of the last k-step (if not issued yet), then the fused final tap;
-            // the last k-step's A prefetch waits for the MFMAs that read the slot it refills
-            if (j + lb < kKStepsRes) read_b(j + lb);
-            load_a(j);
-            final_tap_epilogue<W, CT, NPT, S, DA, DB, EPI, OUT>(smem, g, lane, A, B, bv, acc, hoff, dacc);
-            load_a(j + 1);
-#ifdef SPAI_DIAG_KSTEP
-            if (kst) kst[j] = __builtin_amdgcn_s_memtime();
-#endif
-            break;
-        }
-        load_a(j);
-        const int nr = j + lb < kKStepsRes ? read_b(j + lb) : 0;   // B reads issued this k-step (issue hints)
-        int nm = 0;
-#pragma unroll
-        for (int i = 0; i < PL::n; ++i)
-            if (task_on(i) && live(PL::pt(i), ks)) {
-                const int t = PL::gpt(PL::pt(i));
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(A[j % DA][PL::co(i) - PL::C0]),
-                                                                as_bf16x8(B[j % DB][PL::pt(i)]),
-                                                                ks == first_kstep(S, t) ? bv[PL::co(i) - PL::C0]
-                                                                                        : acc[i], 0, 0, 0);
-                ++nm;
-            }
-        int ndw = 0;   // deferred epilogue tasks stored this k-step (tasks [j n / jb, (j + 1) n / jb))
-        if constexpr (din) {
-#pragma unroll
-            for (int i = 0; i < PL::n; ++i)
-                if (j < jb && i >= j * PL::n / jb && i < (j + 1) * PL::n / jb && PL::deferred(i)) {
-                    const int off = IN + (g.epi[PL::pt(i)] ^ (PL::co(i) << 5));
-                    *(uint2 *)(smem + off) = make_uint2(pack_relu_bf16x2(dacc[i][0], dacc[i][1]),
-                                                        pack_relu_bf16x2(dacc[i][2], dacc[i][3]));
-                    ++ndw;
-                }
-        }
-        // issue order for this k-step: each MFMA followed by up to 2 VALU, one
-        // LDS read (next B) and one weight load (A, DA-1 ahead); deferred stores last
-        const int ng = nm > nr ? nm : nr;
-#pragma unroll
-        for (int i = 0; i < PL::n; ++i) {
-            if (i < ng) {
-                if (i < nm) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-                if (i < nr) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                if (i < CTL) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-        }
-        if constexpr (din) {
-#pragma unroll
-            for (int k = 0; k < PL::n; ++k)
-                if (k < ndw) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#ifdef SPAI_DIAG_KSTEP
-        if (kst) kst[j] = __builtin_amdgcn_s_memtime();
-#endif
-    }
-#endif
 }
 
 template <int CT, int C0, int CTL, int DA>
@@ -1109,21 +734,16 @@ __device__ __forceinline__ void load_a_first(const uint4 *__restrict__ w, int la
 #pragma unroll
     for (int k = 0; k < DA - 1; ++k)
 #pragma unroll
-        for (int c = 0; c < CTL; ++c) A[k][c] = w[(kstep_of(k) * CT + C0 + c) * 64 + lane];
+        for (int c = 0; c < CTL; ++c) A[k][c] = w[(k * CT + C0 + c) * 64 + lane];
 }
 
 // epilogue for a 64-channel bf16 output: relu(acc) -> LDS at OUT (the stem's;
 // the trunk and head convs fuse theirs into the last tap, final_tap_epilogue)
 template <int W, int NPT, int OUT>
-__device__ __forceinline__ void epilogue_act(uint8_t *smem, const Geo<Plan<W, 4, NPT>::NT> &g, f32x4 (&acc)[Plan<W, 4, NPT>::n],
-                                             f32x4 (&dacc)[Plan<W, 4, NPT>::NDA]) {
+__device__ __forceinline__ void epilogue_act(uint8_t *smem, const Geo<Plan<W, 4, NPT>::NT> &g, f32x4 (&acc)[Plan<W, 4, NPT>::n]) {
     using PL = Plan<W, 4, NPT>;
 #pragma unroll
     for (int i = 0; i < PL::n; ++i) {
-        if (PL::deferred(i)) {   // stored by the first trunk conv's K-half-0 k-steps
-            dacc[i] = acc[i];
-            continue;
-        }
         const int off = OUT + (g.epi[PL::pt(i)] ^ (PL::co(i) << 5));
         *(uint2 *)(smem + off) = make_uint2(pack_relu_bf16x2(acc[i][0], acc[i][1]), pack_relu_bf16x2(acc[i][2], acc[i][3]));
     }
@@ -1137,8 +757,7 @@ __device__ __forceinline__ void epilogue_act(uint8_t *smem, const Geo<Plan<W, 4,
 template <int W, int S, bool FROM_X>
 __device__ __forceinline__ void stem(uint8_t *smem, const NetParams &P, const float *__restrict__ x, int base_slot,
                                      int valid, int lane, const Geo<Plan<W, 4, npt_of(S)>::NT> &g,
-                                     const int (&aux)[Plan<W, 4, npt_of(S)>::NT],
-                                     f32x4 (&dacc)[Plan<W, 4, npt_of(S)>::NDA]) {
+                                     const int (&aux)[Plan<W, 4, npt_of(S)>::NT]) {
     constexpr int NPT = npt_of(S);
     using PL = Plan<W, 4, NPT>;
     constexpr int NT = PL::NT;
@@ -1190,7 +809,7 @@ __device__ __forceinline__ void stem(uint8_t *smem, const NetParams &P, const fl
     for (int i = 0; i < PL::n; ++i)
         acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(a[PL::co(i)]), as_bf16x8(bv[PL::pt(i)]),
                                                         b4[PL::co(i)], 0, 0, 0);
-    epilogue_act<W, NPT, kX>(smem, g, acc, dacc);
+    epilogue_act<W, NPT, kX>(smem, g, acc);
 }
 
 // The head conv (64 -> 32 policy + 3 value channels) on the 64-channel layers'
@@ -1202,8 +821,7 @@ __device__ __forceinline__ void head_layer(uint8_t *smem, const NetParams &P, in
                                            const Geo<Plan<W, 4, npt_of(S)>::NT> &g,
                                            const int (&aux)[Plan<W, 4, npt_of(S)>::NT],
                                            uint4 (&A)[DA][Plan<W, 4, npt_of(S)>::CTL],
-                                           uint4 (&wlin)[kLinWPer],
-                                           f32x4 (&dacc)[Plan<W, 4, npt_of(S)>::NDA]) {
+                                           uint4 (&wlin)[kLinWPer]) {
     constexpr int NPT = npt_of(S);
     using PL = Plan<W, 4, NPT>;
     int hoff[PL::NT];   // head-feature offset of each tile's row (-1: padding)
@@ -1216,7 +834,7 @@ __device__ __forceinline__ void head_layer(uint8_t *smem, const NetParams &P, in
     for (int i = 0; i < kLinWPer; ++i) wlin[i] = P.w_lin[(W * kLinWPer + i) * 64 + lane];   // consumed after the head conv
     f32x4 acc[PL::n];
     conv_mfma<W, 4, NPT, S, kX, DA, b_depth(S), 3, kH>(smem, g, (const float *)(smem + kBias) + kHid * (1 + 2 * P.blocks),
-                                                      P.w_head, P.w_head, lane, A, acc, hoff, dacc);
+                                                      P.w_head, P.w_head, lane, A, acc, hoff);
 #ifdef SPAI_DIAG
     if (kDiagHead) stamp(P, W, lane, 17);
 #endif
@@ -1260,136 +878,7 @@ __device__ __forceinline__ void linear_mfma(uint8_t *smem, int lane, const uint4
     }
 }
 
-
-// ---------------------------------------------------------------- split-K trunk conv (SPAI_W8)
-// Plan wave W's tasks over half of K: KH = 1 the k-steps of input channels 0-31
-// of every tap (even k-steps), KH = 2 those of channels 32-63 (odd).  The A
-// ring runs over the wave's 9 local k-steps (DA | 9) and carries the next
-// layer's first ones across the boundary.  Then the two waves of the pair swap
-// partial sums through LDS: each finishes half of the tasks as
-// (first-half sum incl. bias) + (second-half sum), adds the residual by the
-// identity MFMA (EPI = 2) and stores relu/bf16 to OUT.
-template <int W, int NPT>
-__device__ __forceinline__ int split_keep_lo() {
-    return (Plan<W, 4, NPT>::n + 1) / 2;   // tasks [0, h) finish on the KH = 1 wave, [h, n) on the KH = 2 wave
-}
-template <int W, int NPT, int S, int IN, int DA, int DB, int EPI, int OUT, int KH>
-__device__ __forceinline__ void conv_split(uint8_t *smem, const Geo<Plan<W, 4, NPT>::NT> &g, const float *bias,
-                                           const uint4 *__restrict__ w, const uint4 *__restrict__ wn, int lane,
-                                           uint4 (&A)[DA][Plan<W, 4, NPT>::CTL], f32x4 (&acc)[Plan<W, 4, NPT>::n]) {
-#ifdef SPAI_W8
-    using PL = Plan<W, 4, NPT>;
-    constexpr int NT = PL::NT, CTL = PL::CTL, n = PL::n, KL = kKStepsRes / 2, par = KH - 1;
-    static_assert(KH == 1 || KH == 2, "split half");
-    static_assert(KL % DA == 0, "the carried A ring needs DA | local k-steps");
-    static_assert(n <= kSplitMaxN, "partial-sum buffer");
-    const int q = lane >> 4;
-    f32x4 bv[CTL];
-#pragma unroll
-    for (int c = 0; c < CTL; ++c) {
-        if (KH == 1) {
-            const float4 b = *(const float4 *)(bias + (PL::C0 + c) * 16 + 4 * q);
-            bv[c] = f32x4{b.x, b.y, b.z, b.w};
-        } else {
-            bv[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    }
-    const uint4 *wl = w + PL::C0 * 64 + lane;
-    const uint4 *wnl = wn + PL::C0 * 64 + lane;
-    auto live = [](int t, int j) { return !((tap_skip(S, PL::gpt(t)) >> j) & 1); };   // local step j = tap j
-    constexpr int la = DA - 1, lb = DB - 1;
-    uint4 B[DB][NT];
-#pragma unroll
-    for (int j = 0; j < lb; ++j)
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-            if (live(t, j)) B[j][t] = *(const uint4 *)(smem + (IN - 256) + (g.b(t, j) ^ (par << 6)));
-    auto load_a = [&](int j) {
-        const int jj = j + la;
-#pragma unroll
-        for (int c = 0; c < CTL; ++c)
-            A[jj % DA][c] = jj < KL ? wl[((2 * jj + par) * 4 + c) * 64] : wnl[((2 * (jj - KL) + par) * 4 + c) * 64];
-    };
-#pragma unroll
-    for (int j = 0; j < KL; ++j) {
-        load_a(j);
-        int nr = 0;
-        if (j + lb < KL) {
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-                if (live(t, j + lb)) {
-                    B[(j + lb) % DB][t] = *(const uint4 *)(smem + (IN - 256) + (g.b(t, j + lb) ^ (par << 6)));
-                    ++nr;
-                }
-        }
-        int nm = 0;
-#pragma unroll
-        for (int i = 0; i < n; ++i)
-            if (live(PL::pt(i), j)) {
-                const int t = PL::gpt(PL::pt(i));
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(A[j % DA][PL::co(i) - PL::C0]),
-                                                                as_bf16x8(B[j % DB][PL::pt(i)]),
-                                                                2 * j == first_kstep(S, t) ? bv[PL::co(i) - PL::C0]
-                                                                                           : acc[i], 0, 0, 0);
-                ++nm;
-            }
-        const int ng = nm > nr ? nm : nr;
-#pragma unroll
-        for (int i = 0; i < n; ++i) {
-            if (i < ng) {
-                if (i < nm) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-                if (i < nr) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                if (i < CTL) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    // swap half of the partial sums with the partner wave
-    constexpr int h = (n + 1) / 2;
-    constexpr int g0 = KH == 1 ? h : 0, g1 = KH == 1 ? n : h;   // given away
-    constexpr int k0 = KH == 1 ? 0 : h, k1 = KH == 1 ? h : n;   // kept and finished here
-    f32x4 *part = (f32x4 *)(smem + kPart) + (size_t)W * kSplitMaxN * 64 + lane;
-#pragma unroll
-    for (int i = g0; i < g1; ++i) part[i * 64] = acc[i];
-    __syncthreads();
-    uint4 id[2];
-    if (EPI == 2) {
-        const int m = lane & 15;
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-            const int jj = 16 * hh + m - 8 * q;
-            uint32_t wv[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) wv[e] = jj == 2 * e ? 0x3F80u : jj == 2 * e + 1 ? 0x3F800000u : 0u;
-            id[hh] = make_uint4(wv[0], wv[1], wv[2], wv[3]);
-        }
-    }
-#pragma unroll
-    for (int i = k0; i < k1; ++i) {
-        const f32x4 p = part[i * 64];
-        f32x4 a = KH == 1 ? acc[i] + p : p + acc[i];   // (first K half) + (second K half)
-        if (EPI == 2) {
-            const uint4 rb = *(const uint4 *)(smem + (OUT - 256) + (g.b(PL::pt(i), 4) ^ ((PL::co(i) >> 1) << 6)));
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(id[PL::co(i) & 1]), as_bf16x8(rb), a, 0, 0, 0);
-        }
-        const int off = OUT + (g.epi[PL::pt(i)] ^ (PL::co(i) << 5));
-        *(uint2 *)(smem + off) = make_uint2(pack_relu_bf16x2(a[0], a[1]), pack_relu_bf16x2(a[2], a[3]));
-    }
-#else
-    (void)smem, (void)g, (void)bias, (void)w, (void)wn, (void)lane, (void)A, (void)acc;
-#endif
-}
-
-template <int KH, int CTL, int C0, int DA>
-__device__ __forceinline__ void load_a_first_split(const uint4 *__restrict__ w, int lane, uint4 (&A)[DA][CTL]) {
-#pragma unroll
-    for (int j = 0; j < DA - 1; ++j)
-#pragma unroll
-        for (int c = 0; c < CTL; ++c) A[j][c] = w[((2 * j + KH - 1) * 4 + C0 + c) * 64 + lane];
-}
-
-template <int W, int S, bool FROM_X, int KH>
+template <int W, int S, bool FROM_X>
 __device__ __forceinline__ void torso_and_heads(uint8_t *smem, const NetParams &P, const float *__restrict__ x,
                                                 int base, int valid, int lane, const Geo<Plan<W, 4, npt_of(S)>::NT> &g,
                                                 const int (&aux)[Plan<W, 4, npt_of(S)>::NT]) {
@@ -1397,50 +886,12 @@ __device__ __forceinline__ void torso_and_heads(uint8_t *smem, const NetParams &
     using PL4 = Plan<W, 4, NPT>;
     constexpr size_t kLayer = (size_t)kKStepsRes * 4 * 64;
     const float *bias = (const float *)(smem + kBias);
-    if constexpr (KH > 0) {   // SPAI_W8: split-K trunk on 8 waves, stem / head / linear on waves 0-3
-        constexpr int DA = 3, DB = b_depth(S), SW = KH == 2 ? -1 : W;
-        uint4 A[DA][PL4::CTL];
-        if (P.blocks > 0) load_a_first_split<KH, PL4::CTL, PL4::C0, DA>(P.w_res, lane, A);
-        static_assert(!kDefer, "SPAI_W8 has no deferred epilogue");
-        f32x4 dacc[PL4::NDA];
-        if (KH == 1) stem<W, S, FROM_X>(smem, P, x, base, valid, lane, g, aux, dacc);
-        __syncthreads();
-        stamp(P, SW, lane, 1);
-        for (int b = 0; b < P.blocks; ++b) {
-            f32x4 acc[PL4::n];
-            const int l1 = 2 * b, l2 = 2 * b + 1;
-            conv_split<W, NPT, S, kX, DA, DB, 1, kY, KH>(smem, g, bias + kHid * (1 + l1), P.w_res + l1 * kLayer,
-                                                        P.w_res + l2 * kLayer, lane, A, acc);
-            layer_barrier();
-            if (l1 < 12) stamp(P, SW, lane, 2 + l1);
-            conv_split<W, NPT, S, kY, DA, DB, 2, kX, KH>(smem, g, bias + kHid * (1 + l2), P.w_res + l2 * kLayer,
-                                                        b + 1 < P.blocks ? P.w_res + (l2 + 1) * kLayer : P.w_res + l2 * kLayer,
-                                                        lane, A, acc);
-            layer_barrier();
-            if (l2 < 12) stamp(P, SW, lane, 2 + l2);
-        }
-        uint4 wlin[kLinWPer];
-        if (KH == 1) {
-            constexpr int DH = a_depth(S);
-            uint4 Ah[DH][PL4::CTL];
-            load_a_first<4, PL4::C0, PL4::CTL, DH>(P.w_head, lane, Ah);
-            head_layer<W, S, DH>(smem, P, lane, g, aux, Ah, wlin, dacc);
-        }
-        __syncthreads();
-        stamp(P, SW, lane, 14);
-        if (KH == 1) linear_mfma<W, S>(smem, lane, wlin);
-        return;
-    }
     constexpr int DA = a_depth(S), DB = b_depth(S);
     uint4 A[DA][PL4::CTL];
     load_a_first<4, PL4::C0, PL4::CTL, DA>(P.blocks > 0 ? P.w_res : P.w_head, lane, A);
-    f32x4 dacc[PL4::NDA];   // deferred epilogue accumulators, handed from each layer to the next
-    stem<W, S, FROM_X>(smem, P, x, base, valid, lane, g, aux, dacc);
+    stem<W, S, FROM_X>(smem, P, x, base, valid, lane, g, aux);
     __syncthreads();
     stamp(P, W, lane, 1);
-#ifdef SPAI_C4_BLOCK_UNROLL
-#pragma unroll SPAI_C4_BLOCK_UNROLL
-#endif
     for (int b = 0; b < P.blocks; ++b) {   // relu(x + BN(conv(relu(BN(conv(x)))))), model/mod.rs:152-165
         f32x4 acc[Plan<W, 4, NPT>::n];
         const int l1 = 2 * b, l2 = 2 * b + 1;
@@ -1449,7 +900,7 @@ __device__ __forceinline__ void torso_and_heads(uint8_t *smem, const NetParams &
         if (b == 1 && P.stamps && lane == 0) kst = P.stamps + ((size_t)blockIdx.x * kWaves + W) * kStamps + 24;
 #endif
         conv_mfma<W, 4, NPT, S, kX, DA, DB, 1, kY>(smem, g, bias + kHid * (1 + l1), P.w_res + l1 * kLayer,
-                                                                    P.w_res + l2 * kLayer, lane, A, acc, aux, dacc, kst);
+                                                                    P.w_res + l2 * kLayer, lane, A, acc, aux, kst);
 #ifdef SPAI_DIAG_KSTEP
         if (kst) kst[18] = __builtin_amdgcn_s_memtime();
 #endif
@@ -1457,15 +908,11 @@ __device__ __forceinline__ void torso_and_heads(uint8_t *smem, const NetParams &
         if (b == 0 && !kDiagHead && !kDiagEntry) {   // make the k-loop's results visible before the stamp
             asm volatile("" ::"v"(acc[0][0]), "v"(acc[PL4::n - 1][3]));
             stamp(P, W, lane, 17);
-        }
-#endif
-#ifdef SPAI_DIAG
-        if (b == 0 && !kDiagHead && !kDiagEntry) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             stamp(P, W, lane, 18);
         }
 #endif
-        layer_barrier();
+        __syncthreads();
 #ifdef SPAI_DIAG_KSTEP
         if (kst) kst[19] = __builtin_amdgcn_s_memtime();
 #endif
@@ -1474,13 +921,13 @@ __device__ __forceinline__ void torso_and_heads(uint8_t *smem, const NetParams &
 #endif
         if (l1 < 12) stamp(P, W, lane, 2 + l1);
         conv_mfma<W, 4, NPT, S, kY, DA, DB, 2, kX>(smem, g, bias + kHid * (1 + l2), P.w_res + l2 * kLayer,
-                            b + 1 < P.blocks ? P.w_res + (l2 + 1) * kLayer : P.w_head, lane, A, acc, aux, dacc);
-        layer_barrier();
+                            b + 1 < P.blocks ? P.w_res + (l2 + 1) * kLayer : P.w_head, lane, A, acc, aux);
+        __syncthreads();
         if (l2 < 12) stamp(P, W, lane, 2 + l2);
     }
     if (kDiagHead) stamp(P, W, lane, 19);   // diagnostic head mode: 19 = before the head, 17 = head k-loop, 18 = H written
     uint4 wlin[kLinWPer];
-    head_layer<W, S, DA>(smem, P, lane, g, aux, A, wlin, dacc);
+    head_layer<W, S, DA>(smem, P, lane, g, aux, A, wlin);
     __syncthreads();
     stamp(P, W, lane, 14);
     linear_mfma<W, S>(smem, lane, wlin);
@@ -1491,11 +938,11 @@ __device__ __forceinline__ void torso_and_heads(uint8_t *smem, const NetParams &
 // (a group's latency grows with its npt_of(S) position tiles, so e.g. 3000
 // leaves run as 2 rounds of S = 6 (16 tiles), not 2 rounds of S = 8 (21 tiles)).
 __host__ __device__ inline int group_size(uint32_t count, uint32_t grid) {
-    const uint32_t cap = grid * (uint32_t)kSRun;
+    const uint32_t cap = grid * (uint32_t)kS;
     const uint32_t rounds = count ? (count + cap - 1) / cap : 1u;
     const uint32_t per = grid * rounds;
     const int g = (int)((count + per - 1) / per);
-    return g < 1 ? 1 : g > kSRun ? kSRun : g;
+    return g < 1 ? 1 : g > kS ? kS : g;
 }
 
 // Group size when `conc` search chains' forwards share the CUs (conc > 1): their
@@ -1511,23 +958,17 @@ __host__ __device__ inline int group_size(uint32_t count, uint32_t grid) {
 // 58.6k x 0.888).  The results do not depend on S.
 constexpr float kGroupCycles[kS + 1] = {0.f, 29000.f, 43500.f, 52000.f, 62900.f, 81200.f, 86200.f, 94700.f, 100500.f};
 constexpr float kLaunchCycles = 4200.f;   // kernel entry to the first group (~2 us)
-#ifndef SPAI_CONC_CHAIN_CYCLES
-#define SPAI_CONC_CHAIN_CYCLES 31000.f
-#endif
-#ifndef SPAI_CONC_MIN_COUNT
-#define SPAI_CONC_MIN_COUNT 600
-#endif
-constexpr float kChainCycles = SPAI_CONC_CHAIN_CYCLES;   // the chain's tree kernels and launch gaps per iteration (~15 us)
+constexpr float kChainCycles = 31000.f;   // the chain's tree kernels and launch gaps per iteration (~15 us)
 // below this many leaves the chains' forwards are short and the model's CU term
 // overstates their contention: measured slower there (moves 26-41 of a bench step,
 // profiles/r04/group_policy)
-constexpr uint32_t kConcMinCount = SPAI_CONC_MIN_COUNT;
+constexpr uint32_t kConcMinCount = 600;
 __host__ __device__ inline int group_size_conc(uint32_t count, uint32_t grid, int conc) {
     const int s0 = group_size(count, grid);
     if (conc <= 1 || count < kConcMinCount) return s0;
     float best = 3.0e38f;
     int bs = s0;
-    for (int S = s0; S <= kSRun; ++S) {
+    for (int S = s0; S <= kS; ++S) {
         const uint32_t wgs = (count + S - 1) / S, rounds = (wgs + grid - 1) / grid;
         const float cu = (float)wgs * kGroupCycles[S] + (float)(wgs < grid ? wgs : grid) * kLaunchCycles;
         const float lat = (float)rounds * kGroupCycles[S] + kLaunchCycles;
@@ -1541,12 +982,11 @@ __host__ __device__ inline int group_size_conc(uint32_t count, uint32_t grid, in
 }
 
 // The group loop of one (wave, group size) variant.
-template <int W, int S, bool FROM_X, int KH>
+template <int W, int S, bool FROM_X>
 __device__ __forceinline__ void run_groups(uint8_t *smem, const NetParams &P, uint32_t count, int ngroups,
                                            const uint64_t *__restrict__ mine, const uint64_t *__restrict__ theirs,
                                            const float *__restrict__ x, float *__restrict__ priors,
                                            float *__restrict__ value, float *__restrict__ logits, int tid) {
-    constexpr int wave = KH == 2 ? -1 : W;   // (stamps: one wave of each SIMD pair)
     const int lane = tid & 63;
     for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
         // hide the lane id from loop-invariant code motion: the trunk geometry (and
@@ -1573,10 +1013,11 @@ __device__ __forceinline__ void run_groups(uint8_t *smem, const NetParams &P, ui
 #ifdef SPAI_DIAG_ENTRY
         if (grp == (int)blockIdx.x) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            stamp(P, wave, lane, 18);
+            stamp(P, W, lane, 18);
         }
 #endif
-        if (!FROM_X && tid < kStemThreads) {   // neighbour planes N[s][k]: k = tap*3 + plane, shifted so bit b = value at b's neighbour
+        // neighbour planes N[s][k]: k = tap*3 + plane, shifted so bit b = value at b's neighbour
+        if (!FROM_X && tid < kThreads) {   // (the bound keeps s = tid >> 5 below kS)
             const int s = tid >> 5, k = tid & 31;
             uint64_t v = 0;
             if (k < 27 && s < valid) {
@@ -1591,15 +1032,15 @@ __device__ __forceinline__ void run_groups(uint8_t *smem, const NetParams &P, ui
 #ifdef SPAI_DIAG_ENTRY
         if (grp == (int)blockIdx.x) {
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            stamp(P, wave, lane, 19);
+            stamp(P, W, lane, 19);
         }
 #endif
         __syncthreads();
-        stamp(P, wave, lane, 0);
-        if (grp == (int)blockIdx.x) stamp_real(P, wave, lane, 22);
-        torso_and_heads<W, S, FROM_X, KH>(smem, P, x, base, valid, ln, g, aux);
+        stamp(P, W, lane, 0);
+        if (grp == (int)blockIdx.x) stamp_real(P, W, lane, 22);
+        torso_and_heads<W, S, FROM_X>(smem, P, x, base, valid, ln, g, aux);
         __syncthreads();
-        stamp(P, wave, lane, 15);
+        stamp(P, W, lane, 15);
         if (tid < valid) {
             const float *L = (const float *)(smem + kL);
             const int slot = base + tid;
@@ -1642,7 +1083,7 @@ __device__ __forceinline__ void run_groups(uint8_t *smem, const NetParams &P, ui
                 pr[1] = make_float4(out[4], out[5], out[6], 0.f);
             }
         }
-        stamp(P, wave, lane, 16);
+        stamp(P, W, lane, 16);
         __syncthreads();   // kB / planes / L are rewritten by the next group
     }
 }
@@ -1652,24 +1093,12 @@ __device__ __forceinline__ void dispatch_wave(uint8_t *smem, const NetParams &P,
                                               const uint64_t *__restrict__ mine, const uint64_t *__restrict__ theirs,
                                               const float *__restrict__ x, float *__restrict__ priors,
                                               float *__restrict__ value, float *__restrict__ logits, int wave, int tid) {
-#ifdef SPAI_W8
-    constexpr int K0 = 1, K1 = 2;   // waves 0-3: the first K half of each tap, 4-7: the second
-#else
-    constexpr int K0 = 0;
-#endif
     switch (wave) {
-    case 0: run_groups<0, S, FROM_X, K0>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, tid); break;
-    case 1: run_groups<1, S, FROM_X, K0>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, tid); break;
-    case 2: run_groups<2, S, FROM_X, K0>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, tid); break;
-    case 3: run_groups<3, S, FROM_X, K0>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, tid); break;
-#ifdef SPAI_W8
-    case 4: run_groups<0, S, FROM_X, K1>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, tid); break;
-    case 5: run_groups<1, S, FROM_X, K1>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, tid); break;
-    case 6: run_groups<2, S, FROM_X, K1>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, tid); break;
-    default: run_groups<3, S, FROM_X, K1>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, tid); break;
-#else
+    case 0: run_groups<0, S, FROM_X>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, tid); break;
+    case 1: run_groups<1, S, FROM_X>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, tid); break;
+    case 2: run_groups<2, S, FROM_X>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, tid); break;
+    case 3: run_groups<3, S, FROM_X>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, tid); break;
     default: break;
-#endif
     }
 }
 
@@ -1690,52 +1119,40 @@ __global__ __launch_bounds__(kThreads) void k_forward(const uint32_t *__restrict
     // launch constants (stem weights, every conv bias): their loads are issued
     // together, beside the leaf count's, and land in LDS before the group loop
     // (staged inside it they were two more dependent round trips per launch)
-    const bool setup = kThreads == kStemThreads || tid < kStemThreads;
-    const uint4 ws = setup ? P.w_stem[tid] : make_uint4(0u, 0u, 0u, 0u);   // 256 x 16 B
-    const int nbias = setup ? (2 * P.blocks + 2) * kHid : 0;
+    const uint4 ws = P.w_stem[tid];   // 256 x 16 B
+    const int nbias = (2 * P.blocks + 2) * kHid;
     float bv[kBiasPer];
 #pragma unroll
-    for (int j = 0; j < kBiasPer; ++j) bv[j] = tid + j * kStemThreads < nbias ? P.b_conv[tid + j * kStemThreads] : 0.f;
+    for (int j = 0; j < kBiasPer; ++j) bv[j] = tid + j * kThreads < nbias ? P.b_conv[tid + j * kThreads] : 0.f;
     const uint32_t count = count_ptr ? *count_ptr : count_imm;
-    const int S = force_s > 0 ? min(force_s, kSRun) : group_size_conc(count, gridDim.x, conc);
+    const int S = force_s > 0 ? min(force_s, kS) : group_size_conc(count, gridDim.x, conc);
     const int ngroups = (int)((count + S - 1) / S);
     if ((int)blockIdx.x >= ngroups) return;
     if (tid < 64) ((uint32_t *)(smem + kZ))[tid] = 0u;   // the zero blocks below X and Y
     else if (tid < 128) ((uint32_t *)(smem + kZ1))[tid - 64] = 0u;
-    if (setup) ((uint4 *)(smem + kWStem))[tid] = ws;
+    ((uint4 *)(smem + kWStem))[tid] = ws;
 #pragma unroll
     for (int j = 0; j < kBiasPer; ++j)
-        if (tid + j * kStemThreads < nbias) ((float *)(smem + kBias))[tid + j * kStemThreads] = bv[j];
+        if (tid + j * kThreads < nbias) ((float *)(smem + kBias))[tid + j * kThreads] = bv[j];
 #ifdef SPAI_DIAG_ENTRY
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     stamp(P, tid >> 6, tid & 63, 17);
 #endif
-#ifdef SPAI_FWD_PRIO
-    __builtin_amdgcn_s_setprio(SPAI_FWD_PRIO);   // experiment: issue priority against co-resident tree kernels
-#endif
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     if constexpr (FROM_X) {
-        dispatch_wave<kSRun, true>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, wave, tid);
+        dispatch_wave<kS, true>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, wave, tid);
     } else {
-#ifdef SPAI_ONLY_S
-        dispatch_wave<SPAI_ONLY_S, false>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, wave, tid);
-#else
         switch (S) {
         case 1: dispatch_wave<1, false>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, wave, tid); break;
         case 2: dispatch_wave<2, false>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, wave, tid); break;
         case 3: dispatch_wave<3, false>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, wave, tid); break;
         case 4: dispatch_wave<4, false>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, wave, tid); break;
-#ifdef SPAI_W8
-        default: dispatch_wave<5, false>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, wave, tid); break;
-#else
         case 5: dispatch_wave<5, false>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, wave, tid); break;
         case 6: dispatch_wave<6, false>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, wave, tid); break;
         case 7: dispatch_wave<7, false>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, wave, tid); break;
         default: dispatch_wave<8, false>(smem, P, count, ngroups, mine, theirs, x, priors, value, logits, wave, tid); break;
-#endif
         }
-#endif
     }
     stamp_real(P, wave, tid & 63, 23);
 }
@@ -2075,7 +1492,7 @@ int net_phase_stamps(spai_net *n, uint32_t cnt, double *cycles) {
     std::vector<uint64_t> m, t;
     random_positions(cnt, m, t);
     const char *es = std::getenv("SPAI_PHASE_S");   // diagnostic: group size to time (default 8)
-    const int S = es ? std::max(1, std::min(kSRun, std::atoi(es))) : kSRun;
+    const int S = es ? std::max(1, std::min(kS, std::atoi(es))) : kS;
     uint32_t grid = (cnt + S - 1) / S;
     if (const char *eg = std::getenv("SPAI_PHASE_GRID"))   // fewer workgroups: the stamps keep each one's LAST group
         grid = std::min<uint32_t>(grid, (uint32_t)std::max(1, std::atoi(eg)));
@@ -2139,7 +1556,7 @@ int net_eval_batch(spai_net *net, hipStream_t st, const uint32_t *d_count, uint3
     // SPAI_FWD_S=k: every launch at group size k (A/B knob; the results do not depend on S)
     static const int force_s = [] {
         const char *v = std::getenv("SPAI_FWD_S");
-        return v ? std::max(0, std::min(kSRun, std::atoi(v))) : 0;
+        return v ? std::max(0, std::min(kS, std::atoi(v))) : 0;
     }();
     k_forward<false><<<grid, kThreads, 0, st>>>(d_count, max_n, force_s, conc_policy ? conc : 1, mine, theirs, nullptr,
                                                 params_of(net), priors, value, nullptr);
@@ -2156,7 +1573,7 @@ int net_forward_x(spai_net *n, uint32_t cnt, const float *x, float *logits, floa
     if (n->dtype == SPAI_DTYPE_F32) {
         SPAI_TRY(net_f32_launch(n, st, nullptr, cnt, nullptr, nullptr, n->io_x.p, nullptr, n->io_value.p, n->io_logits.p));
     } else {
-        k_forward<true><<<(cnt + kSRun - 1) / kSRun, kThreads, 0, st>>>(nullptr, cnt, kSRun, 1, nullptr, nullptr, n->io_x.p,
+        k_forward<true><<<(cnt + kS - 1) / kS, kThreads, 0, st>>>(nullptr, cnt, kS, 1, nullptr, nullptr, n->io_x.p,
                                                                  params_of(n), nullptr, n->io_value.p, n->io_logits.p);
         SPAI_HIP(hipGetLastError());
     }

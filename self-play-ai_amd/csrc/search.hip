@@ -34,10 +34,7 @@ namespace spai {
 namespace {
 
 constexpr int kLanesPerTree = 8;
-#ifndef SPAI_TREE_BLOCK
-#define SPAI_TREE_BLOCK 64
-#endif
-constexpr int kBlock = SPAI_TREE_BLOCK;   // threads per tree-kernel workgroup (kBlock / 8 trees)
+constexpr int kBlock = 64;   // threads per tree-kernel workgroup (kBlock / 8 trees)
 constexpr int kTreesPerBlock = kBlock / kLanesPerTree;
 constexpr uint32_t kErrNan = 1u, kErrCapacity = 2u, kErrDepth = 4u;
 
@@ -460,9 +457,6 @@ __global__ __launch_bounds__(kBlock) void k_select(TreeView T, BatchView B, Cach
                                                    const uint32_t *__restrict__ active, uint32_t n_active, float c,
                                                    uint32_t *err, uint32_t run_cap) {
     const uint32_t gi = (blockIdx.x * blockDim.x + threadIdx.x) / kLanesPerTree;
-#ifdef SPAI_TREE_PRIO
-    __builtin_amdgcn_s_setprio(SPAI_TREE_PRIO);   // experiment: issue priority against the co-resident forward
-#endif
     if (gi >= n_active) return;
     const uint32_t t = active[gi];
     RootInfo root = load_root(T, t);
@@ -480,9 +474,6 @@ __global__ __launch_bounds__(kBlock) void k_expand_select(TreeView T, BatchView 
                                                           const uint32_t *__restrict__ active, uint32_t n_active,
                                                           float c, uint32_t *err, uint32_t run_cap) {
     const uint32_t gi = (blockIdx.x * blockDim.x + threadIdx.x) / kLanesPerTree;
-#ifdef SPAI_TREE_PRIO
-    __builtin_amdgcn_s_setprio(SPAI_TREE_PRIO);
-#endif
     if (gi >= n_active) return;
     const int lane8 = threadIdx.x & (kLanesPerTree - 1);
     const uint32_t t = active[gi];

@@ -41,3 +41,22 @@ def test_c4_forward_register_budget(descriptors):
         if "k_forwardILb0E" in n:
             assert int(f["vgpr_count"]) <= 464, (n, f["vgpr_count"])
             assert int(f["vgpr_spill_count"]) == 0, (n, f["vgpr_spill_count"])
+
+
+def test_no_compile_time_variants_in_kernels():
+    """The kernels carry no experiment behind a preprocessor switch: a measured and
+    rejected variant lives in git history and DESIGN.md, not in the product source.
+    Only the diagnostic (phase-stamp) family may be a conditional on an SPAI_ macro."""
+    import glob
+    import re
+    cond = re.compile(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b(.*)$")
+    files = sorted(glob.glob(os.path.join(REPO, "self-play-ai_amd", "csrc", "*.hip")))
+    assert files
+    bad = []
+    for path in files:
+        for no, line in enumerate(open(path), 1):
+            m = cond.match(line)
+            for macro in re.findall(r"\bSPAI_\w+", m.group(1)) if m else []:
+                if not macro.startswith("SPAI_DIAG"):
+                    bad.append("%s:%d: %s" % (os.path.basename(path), no, macro))
+    assert not bad, bad
