@@ -218,8 +218,9 @@ int spai_selfplay_stream(spai_engine *eng, uint32_t n_games, uint32_t window, ui
  * through the forward again.  A hit returns the very bytes a forward wrote for
  * that position, so no result depends on the cache, its size or its state.
  * It is cleared by spai_engine_set_net (new weights) and, between search
- * calls, when it is more than 3/4 full.  Default capacity: 16384 entries per
- * tree slot of cfg.max_trees (64 B each, at most 4 GiB); the environment
+ * calls, when it is more than 7/8 full.  Default capacity: 16384 entries per
+ * tree slot of cfg.max_trees (64 B each, at most 1/16 of the device's total
+ * memory, rounded down to a power of two of buckets); the environment
  * variable SPAI_EVAL_CACHE=<entries> overrides the default (0: off).
  * spai_selfplay_stats.evals counts served leaves (hits included);
  * spai_engine_timing_items counts the leaves the forward launches ran. */
@@ -231,7 +232,7 @@ typedef struct spai_eval_cache_stats {
     double lookups;     /* live leaves looked up (= evals while the cache is on) */
     double hits;        /* of them served from the table */
     double inserts;     /* entries written */
-    double dropped;     /* inserts given up: the position's bucket was full */
+    double dropped;     /* inserts given up: both of the position's buckets were full */
     double clears;      /* times the table was emptied (set_net, fill threshold, resize) */
     double capacity;    /* entries of the table now (0: off) */
 } spai_eval_cache_stats;

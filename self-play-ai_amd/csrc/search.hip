@@ -51,6 +51,11 @@ constexpr uint32_t kErrNan = 1u, kErrCapacity = 2u, kErrDepth = 4u;
 // Every 8-byte word carries a non-zero mark: the generation (1..32767) above
 // the 49 board bits of the key words, the sign bit of the even prior (priors are
 // >= +0; an entry whose priors are not is never inserted) in the payload words.
+// A position has two candidate buckets (cache_buckets): a lookup reads both in
+// one round trip, an insert takes a way of the emptier one, so that a bucket
+// fills up only when both do (at 3/4 load 7 % of the keys find their one bucket
+// full, 0.001 % both of two: scripts/eval_cache_hitrate.py, bucket_loss).  The
+// same position in both buckets (two writers at once) is a harmless duplicate.
 //
 // Protocol (no fence anywhere): an entry is claimed by one agent-scope CAS of
 // word 0 from empty and then written once, by the claimer alone; nothing is
@@ -248,51 +253,77 @@ __device__ __forceinline__ Descent descend(const TreeView &T, uint32_t t, const 
     return kLive;
 }
 
-__device__ __forceinline__ uint4 *cache_way(const CacheView &C, uint64_t mine, uint64_t theirs, int way) {
+// The position's two candidate buckets: the high and the low half of one hash, and
+// first ^ 1 where the halves agree.  A one-bucket table has a single candidate
+// (b1 == b0).
+struct CacheBuckets {
+    uint32_t b0, b1;
+};
+__device__ __forceinline__ CacheBuckets cache_buckets(const CacheView &C, uint64_t mine, uint64_t theirs) {
     const uint64_t h = c4::splitmix64(mine ^ (theirs * 0x9E3779B97F4A7C15ull));
-    const uint32_t bucket = (uint32_t)(h >> 32) & C.mask;
+    const uint32_t b0 = (uint32_t)(h >> 32) & C.mask, b1 = (uint32_t)h & C.mask;
+    return CacheBuckets{b0, b1 == b0 ? (b0 ^ 1u) & C.mask : b1};
+}
+__device__ __forceinline__ uint4 *cache_way(const CacheView &C, uint32_t bucket, int way) {
     return C.tab + ((size_t)bucket * EvalCache::kWays + (uint32_t)way) * 4;
 }
 
+// what cache_claim found
+enum Claim { kClaimFull, kClaimDone, kClaimSame };
+// lane 0's part of an insert into one bucket: claim, by compare-and-swap from 0, the
+// first way that is still empty, starting at the first one the tree's lanes saw empty
+// (`empty`, none: the bucket is full) and going on to the next when another writer got
+// there first; then write the entry.  A way that holds this position's word 0 by now
+// ends it (kClaimSame).
+__device__ __forceinline__ Claim cache_claim(uint4 *bucket, uint32_t empty, uint64_t k0, uint64_t k1, const uint4 &e1,
+                                             const uint4 &e2) {
+    for (int w = empty ? __ffs(empty) - 1 : (int)EvalCache::kWays; w < (int)EvalCache::kWays; ++w) {
+        uint4 *e = bucket + 4 * w;
+        const unsigned long long old = atomicCAS((unsigned long long *)e, 0ull, (unsigned long long)k0);
+        if (old == 0ull) {
+            ((uint64_t *)e)[1] = k1;
+            e[1] = e1;
+            e[2] = e2;
+            return kClaimDone;
+        }
+        if (old == k0) return kClaimSame;
+    }
+    return kClaimFull;
+}
+
 // Insert the evaluated leaf in slot s of batch B, by its tree's 8 lanes: each
-// reads one way's claim word; a way that already holds this position's word 0
-// ends it (the same position, or one that shares `mine` in this bucket: only an
-// insert is lost); else lane 0 claims the first empty way (going on to the next
-// when another writer got there first) and writes the entry.  A full bucket
-// drops the insert.  Returns true in lane 0 when an entry was claimed.
+// reads one way's claim word in both of the position's buckets; a way that
+// already holds this position's word 0 ends it (the same position, or one that
+// shares `mine` in these buckets: only an insert is lost); else lane 0 claims the
+// first empty way of the bucket with more empty ways (ties: the first bucket),
+// and when other writers have filled that bucket in the meantime, of the other
+// one.  Both buckets full drops the insert.  No entry is ever overwritten.
+// Returns true in lane 0 when an entry was claimed.
 __device__ __forceinline__ bool cache_insert(const CacheView &C, const BatchView &B, uint32_t s, int lane8) {
     const uint64_t mine = B.mine[s], theirs = B.theirs[s];
     const uint64_t gen = (uint64_t)C.gen << kGenShift;
     const uint64_t k0 = mine | gen, k1 = theirs | gen;
-    uint4 *bucket = cache_way(C, mine, theirs, 0);
-    const uint64_t seen = *(const uint64_t *)(bucket + 4 * lane8);
+    const CacheBuckets cb = cache_buckets(C, mine, theirs);
+    uint4 *bk0 = cache_way(C, cb.b0, 0), *bk1 = cache_way(C, cb.b1, 0);
+    const uint64_t seen0 = *(const uint64_t *)(bk0 + 4 * lane8);
+    const uint64_t seen1 = *(const uint64_t *)(bk1 + 4 * lane8);
     const float4 pa = *(const float4 *)(B.priors + (size_t)s * kPriorStride);
     const float4 pb = *(const float4 *)(B.priors + (size_t)s * kPriorStride + 4);
     const float value = B.value[s];
-    const uint32_t same = group_bits(__ballot(seen == k0));
-    const uint32_t empty = group_bits(__ballot(seen == 0ull));
+    const uint32_t same = group_bits(__ballot(seen0 == k0 || seen1 == k0));
+    const uint32_t empty0 = group_bits(__ballot(seen0 == 0ull));
+    const uint32_t empty1 = cb.b1 != cb.b0 ? group_bits(__ballot(seen1 == 0ull)) : 0u;
     if (same || lane8 != 0) return false;
     const uint32_t p0 = __float_as_uint(pa.x), p2 = __float_as_uint(pa.z), p4 = __float_as_uint(pb.x),
                    p6 = __float_as_uint(pb.z);
-    bool claimed = false, skip = ((p0 | p2 | p4 | p6) & kPriorMark) != 0u;   // (a marked prior cannot be stored)
-    if (!skip)
-        for (int w = empty ? __ffs(empty) - 1 : (int)EvalCache::kWays; w < (int)EvalCache::kWays; ++w) {
-            uint4 *e = bucket + 4 * w;
-            const unsigned long long old = atomicCAS((unsigned long long *)e, 0ull, (unsigned long long)k0);
-            if (old == 0ull) {
-                ((uint64_t *)e)[1] = k1;
-                e[1] = make_uint4(p0 | kPriorMark, __float_as_uint(pa.y), p2 | kPriorMark, __float_as_uint(pa.w));
-                e[2] = make_uint4(p4 | kPriorMark, __float_as_uint(pb.y), p6 | kPriorMark, __float_as_uint(value));
-                claimed = true;
-                break;
-            }
-            if (old == k0) {
-                skip = true;
-                break;
-            }
-        }
-    if (!claimed && !skip) atomicAdd(C.ctr + 1, 1u);
-    return claimed;
+    if (((p0 | p2 | p4 | p6) & kPriorMark) != 0u) return false;   // (a marked prior cannot be stored)
+    const uint4 e1 = make_uint4(p0 | kPriorMark, __float_as_uint(pa.y), p2 | kPriorMark, __float_as_uint(pa.w));
+    const uint4 e2 = make_uint4(p4 | kPriorMark, __float_as_uint(pb.y), p6 | kPriorMark, __float_as_uint(value));
+    const bool second = c4::popc32(empty1) > c4::popc32(empty0);
+    Claim r = cache_claim(second ? bk1 : bk0, second ? empty1 : empty0, k0, k1, e1, e2);
+    if (r == kClaimFull && cb.b1 != cb.b0) r = cache_claim(second ? bk0 : bk1, second ? empty0 : empty1, k0, k1, e1, e2);
+    if (r == kClaimFull) atomicAdd(C.ctr + 1, 1u);
+    return r == kClaimDone;
 }
 // the fill counter, one atomic per wave: the wave's claims (lane 0 of each tree's group)
 __device__ __forceinline__ void cache_count(const CacheView &C, bool claimed) {
@@ -301,8 +332,15 @@ __device__ __forceinline__ void cache_count(const CacheView &C, bool claimed) {
         atomicAdd(C.ctr, (uint32_t)c4::popc64(b));
 }
 
+// the acceptance test of a lookup: both key words are the position's at this
+// generation, and all four payload marks are there (the entry is complete)
+__device__ __forceinline__ bool cache_holds(const uint4 &q0, const uint4 &q1, const uint4 &q2, uint64_t k0, uint64_t k1) {
+    return (((uint64_t)q0.y << 32) | q0.x) == k0 && (((uint64_t)q0.w << 32) | q0.z) == k1 &&
+           (q1.x & q1.z & q2.x & q2.z & kPriorMark) != 0u;
+}
+
 // live leaf -> batch slot (mcts.rs:249-250).  With the evaluation cache, the
-// tree's 8 lanes first read the 8 ways of the position's bucket (one round
+// tree's 8 lanes first read the 8 ways of the position's two buckets (one round
 // trip): when a way holds the position, complete, the leaf is served from it
 // -- a slot from the top of the batch (cap - 1 downwards, counted in B.hits),
 // with the position, priors and value the forward would have written there --
@@ -315,12 +353,15 @@ __device__ __forceinline__ void slot_leaf(const TreeView &T, const BatchView &B,
     if (lane8 == 0)
         __hip_atomic_fetch_add(T.evals + t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // result unused: no wait
     if (C.tab) {
-        const uint4 *e = cache_way(C, mine, theirs, lane8);
-        const uint4 q0 = e[0], q1 = e[1], q2 = e[2];
+        // both buckets' loads go out together: one round trip, as with one bucket
+        const CacheBuckets cb = cache_buckets(C, mine, theirs);
+        const uint4 *ea = cache_way(C, cb.b0, lane8), *eb = cache_way(C, cb.b1, lane8);
+        const uint4 a0 = ea[0], a1 = ea[1], a2 = ea[2], b0 = eb[0], b1 = eb[1], b2 = eb[2];
         const uint64_t gen = (uint64_t)C.gen << kGenShift;
-        const bool match = (((uint64_t)q0.y << 32) | q0.x) == (mine | gen) &&
-                           (((uint64_t)q0.w << 32) | q0.z) == (theirs | gen) &&
-                           (q1.x & q1.z & q2.x & q2.z & kPriorMark) != 0u;
+        const uint64_t k0 = mine | gen, k1 = theirs | gen;
+        const bool match_a = cache_holds(a0, a1, a2, k0, k1), match_b = cache_holds(b0, b1, b2, k0, k1);
+        const bool match = match_a || match_b;
+        const uint4 q1 = match_a ? a1 : b1, q2 = match_a ? a2 : b2;
         const uint32_t hit = group_bits(__ballot(match));
         if (hit) {
             // lane 0 takes the slot and records it (T.slot is lane 0's word: select_tree's
@@ -603,7 +644,8 @@ int cache_clear(spai_engine *e) {
 }
 
 // Resolve the capacity (spai_eval_cache_set_capacity, else SPAI_EVAL_CACHE=<entries>, else
-// kEntriesPerTree per tree slot of max_trees) and allocate the table, on the first search
+// kEntriesPerTree per tree slot of max_trees, at most 1 / kDefaultDeviceShare of the device's
+// memory; either way rounded down to a power of two of buckets) and allocate the table, on the first search
 // call after a change; on for the net evaluator only.  The counters outlive a resize:
 // the old table's claims are added to the host's total and the device count starts again.
 // (for_net: a net evaluates in the coming call -- cfg.eval for search and self-play, either
@@ -617,8 +659,13 @@ int cache_prepare(spai_engine *e, bool for_net) {
         const char *v = std::getenv("SPAI_EVAL_CACHE");
         if (C.user_set) want = C.requested;
         else if (v) want = std::strtoull(v, nullptr, 10);
-        else want = std::min<uint64_t>(EvalCache::kEntriesPerTree * std::max(1u, e->cfg.max_trees),
-                                       EvalCache::kDefaultMaxEntries);
+        else {
+            // (the total, not what is free now: the size does not depend on what else is allocated)
+            size_t free_bytes = 0, total_bytes = 0;
+            SPAI_HIP(hipMemGetInfo(&free_bytes, &total_bytes));
+            want = std::min<uint64_t>(EvalCache::kEntriesPerTree * std::max(1u, e->cfg.max_trees),
+                                      total_bytes / EvalCache::kDefaultDeviceShare / EvalCache::kEntryBytes);
+        }
     }
     uint32_t buckets = 0;
     if (want) {
@@ -934,7 +981,7 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
     const int kind = (int)e->cfg.eval;
     hipStream_t st = e->stream;
     // evaluation cache: allocated on first use; emptied here, between search calls
-    // (no chain runs), once it is more than 3/4 full, so a long stream keeps hitting
+    // (no chain runs), once it is more than 7/8 full, so a long stream keeps hitting
     SPAI_TRY(cache_prepare(e, kind == SPAI_EVAL_NET));
     if (cache_nearly_full(e->cache)) SPAI_TRY(cache_clear(e));
     // tail mode (select_tree RUN_ON, one chain): late in a game, when in the previous

@@ -166,8 +166,9 @@ inline RootsOut roots_out(spai_engine *e) {
 }
 int cache_prepare(spai_engine *e, bool for_net);
 int cache_clear(spai_engine *e);
-// more than 3/4 full: time to empty it, between search calls
-inline bool cache_nearly_full(const EvalCache &C) { return C.buckets && (uint64_t)C.fill_seen * 4 > C.entries() * 3; }
+// more than 7/8 full: time to empty it, between search calls (with two candidate buckets per
+// position 0.4 % of the inserts find both full at that load; one bucket lost 7 % at 3/4)
+inline bool cache_nearly_full(const EvalCache &C) { return C.buckets && (uint64_t)C.fill_seen * 8 > C.entries() * 7; }
 // a call's leaves: `served` live ones, `forwarded` of them through the net; the table's fill after it
 void cache_account(spai_engine *e, double served, double forwarded, uint32_t fill);
 int check_device_errors(spai_engine *e, uint32_t err);

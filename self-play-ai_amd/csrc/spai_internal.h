@@ -131,7 +131,8 @@ struct Batch {
 struct EvalCache {
     static constexpr uint32_t kWays = 8;
     static constexpr uint64_t kEntriesPerTree = 16384;    // default capacity per tree slot (cfg.max_trees): 1 MiB
-    static constexpr uint64_t kDefaultMaxEntries = 1ull << 26;   // 4 GiB
+    static constexpr uint64_t kEntryBytes = 64;
+    static constexpr uint64_t kDefaultDeviceShare = 16;   // the default takes at most 1/16 of the device's total memory
     static constexpr uint32_t kMinDefaultBuckets = 1024;  // a default table that does not fit is halved down to this
     bool user_set = false;          // capacity set through spai_eval_cache_set_capacity (else SPAI_EVAL_CACHE / default)
     uint64_t requested = 0;         // user_set: entries asked for (0: off)
