@@ -217,8 +217,10 @@ int spai_selfplay_stream(spai_engine *eng, uint32_t n_games, uint32_t window, ui
  * transpositions inside a tree) is served from the table instead of going
  * through the forward again.  A hit returns the very bytes a forward wrote for
  * that position, so no result depends on the cache, its size or its state.
- * It is cleared by spai_engine_set_net (new weights) and, between search
- * calls, when it is more than 7/8 full.  Default capacity: 16384 entries per
+ * It is cleared by spai_engine_set_net (new weights); between search calls,
+ * when it is more than 7/8 full, it is thinned to at most half its capacity
+ * (SPAI_EVAL_CACHE_KEEP=<fraction> for measurements): the entries that were
+ * ever hit and the newest stay (a match empties it instead).  Default capacity: 16384 entries per
  * tree slot of cfg.max_trees (64 B each, at most 1/16 of the device's total
  * memory, rounded down to a power of two of buckets); the environment
  * variable SPAI_EVAL_CACHE=<entries> overrides the default (0: off).
@@ -233,11 +235,24 @@ typedef struct spai_eval_cache_stats {
     double hits;        /* of them served from the table */
     double inserts;     /* entries written */
     double dropped;     /* inserts given up: both of the position's buckets were full */
-    double clears;      /* times the table was emptied (set_net, fill threshold, resize) */
+    double clears;      /* times the table was emptied (set_net, resize, a match's fill threshold) or
+                         * thinned (fill threshold, spai_eval_cache_thin): thinnings included */
     double capacity;    /* entries of the table now (0: off) */
+    double thins;       /* thinnings */
+    double evicted;     /* entries removed by thinnings */
+    double live;        /* entries in the table now */
+    double kept_hit;    /* entries a lookup had ever hit among those the latest thinning kept */
 } spai_eval_cache_stats;
 /* totals since the engine was created; waits for the engine's stream */
 int spai_eval_cache_get_stats(spai_engine *eng, spai_eval_cache_stats *out);
+/* Thin the table now to at most keep_entries entries, by the rule of the fill
+ * threshold: entries that were ever hit first (at most 3/4 of keep_entries), then
+ * the newest never-hit ones, in whole classes of equal age (in search calls), so
+ * fewer may stay.  The survivors stay valid (no new generation).  0 empties the
+ * table; a value at or above the live count evicts nothing.  For a caller that
+ * wants memory pressure relieved, or the table pruned, without losing what it
+ * learnt.  Waits for the engine's stream. */
+int spai_eval_cache_thin(spai_engine *eng, uint64_t keep_entries);
 
 /* ------------------------------------------------------------------ match
  * play() (main.rs:54-135) with a second evaluator in the human's seat, over

@@ -1,7 +1,9 @@
 """The evaluation cache's own counters at the benchmark's scale: one warm-up step,
 then one self_play of FS_STEPS (20) x 4,096 games streamed through 4,096 slots
 (800 sims, 6x64), and spai_eval_cache_get_stats over that call -> one JSON line.
-SPAI_LIB chooses the library, SPAI_EVAL_CACHE the capacity (profiles/eval_cache_two_choice).
+SPAI_LIB chooses the library, SPAI_EVAL_CACHE the capacity (profiles/eval_cache_two_choice);
+SPAI_EVAL_CACHE_THIN_LOG=1 adds one line per thinning on stderr: the classes' sizes and
+what was kept of each (profiles/eval_cache_thin).
 
   python3 scripts/eval_cache_fullstats.py
 """
@@ -18,7 +20,7 @@ t0 = time.perf_counter()
 _, st = e.self_play(STEPS * G, game_id_base=G, collect=False, window=G)
 dt = time.perf_counter() - t0
 c1 = e.eval_cache_stats()
-d = {k: (c1[k] - c0[k] if k != "capacity" else c1[k]) for k in c1}
+d = {k: (c1[k] if k in ("capacity", "live", "kept_hit") else c1[k] - c0[k]) for k in c1}   # states, else totals
 d["hit_rate"] = d["hits"] / d["lookups"]
 d["drop_share_of_attempts"] = d["dropped"] / (d["inserts"] + d["dropped"])
 d["sims_per_sec"] = st["sims"] / dt

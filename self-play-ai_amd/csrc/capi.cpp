@@ -337,6 +337,11 @@ int spai_eval_cache_get_stats(spai_engine *e, spai_eval_cache_stats *out) {
     return eval_cache_stats(e, out);
 }
 
+int spai_eval_cache_thin(spai_engine *e, uint64_t keep_entries) {
+    ENG_CHECK(e);
+    return eval_cache_thin(e, keep_entries);
+}
+
 int spai_trees_create(spai_engine *e, uint32_t n) { ENG_CHECK(e); return trees_create(e, n); }
 int spai_tree_reset(spai_engine *e, uint32_t t, const spai_c4_state *root) { ENG_CHECK(e); return tree_reset(e, t, root); }
 int spai_search(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, float *policy,

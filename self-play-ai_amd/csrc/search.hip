@@ -25,6 +25,7 @@
 // The host only sees the trees between moves: root visit counts come back once
 // per search call, or the record of a move step that ran on the device.
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -56,11 +57,19 @@ constexpr uint32_t kErrNan = 1u, kErrCapacity = 2u, kErrDepth = 4u;
 // fills up only when both do (at 3/4 load 7 % of the keys find their one bucket
 // full, 0.001 % both of two: scripts/eval_cache_hitrate.py, bucket_loss).  The
 // same position in both buckets (two writers at once) is a harmless duplicate.
+// The entry's last quarter holds two stamps that no lookup ever reads, sequence
+// numbers of search calls (CacheView::seq):
+//   word 6 low   born: the call in which the entry was claimed (the claimer's store)
+//   word 6 high  hit:  the latest call in which a lookup accepted it, 0 if none
+//                (one plain 4-byte store by the lane that holds the matching way;
+//                every writer of one call stores the same value)
+// They rank the entries when the table is thinned ("thinning", below).
 //
 // Protocol (no fence anywhere): an entry is claimed by one agent-scope CAS of
-// word 0 from empty and then written once, by the claimer alone; nothing is
-// overwritten until the table is cleared, and it is cleared only by a
-// stream-ordered memset while no search kernel runs.  So whatever a reader sees
+// word 0 from empty and then written once, by the claimer alone; its six key
+// and payload words are not overwritten until the table is cleared or thinned,
+// and that happens only in stream order while no search kernel runs (a memset,
+// or the sweep that zeroes whole entries).  So whatever a reader sees
 // of an entry -- its L1 is per CU, the L2s per XCD, the other chain may be
 // writing it right now -- is a subset of the entry's final words, the rest
 // zero.  The reader accepts only when all six words are marked and both key
@@ -276,7 +285,7 @@ enum Claim { kClaimFull, kClaimDone, kClaimSame };
 // there first; then write the entry.  A way that holds this position's word 0 by now
 // ends it (kClaimSame).
 __device__ __forceinline__ Claim cache_claim(uint4 *bucket, uint32_t empty, uint64_t k0, uint64_t k1, const uint4 &e1,
-                                             const uint4 &e2) {
+                                             const uint4 &e2, uint32_t seq) {
     for (int w = empty ? __ffs(empty) - 1 : (int)EvalCache::kWays; w < (int)EvalCache::kWays; ++w) {
         uint4 *e = bucket + 4 * w;
         const unsigned long long old = atomicCAS((unsigned long long *)e, 0ull, (unsigned long long)k0);
@@ -284,6 +293,7 @@ __device__ __forceinline__ Claim cache_claim(uint4 *bucket, uint32_t empty, uint
             ((uint64_t *)e)[1] = k1;
             e[1] = e1;
             e[2] = e2;
+            *(uint32_t *)(e + 3) = seq;   // born (4 bytes: the hit stamp beside it may be a reader's already)
             return kClaimDone;
         }
         if (old == k0) return kClaimSame;
@@ -320,8 +330,9 @@ __device__ __forceinline__ bool cache_insert(const CacheView &C, const BatchView
     const uint4 e1 = make_uint4(p0 | kPriorMark, __float_as_uint(pa.y), p2 | kPriorMark, __float_as_uint(pa.w));
     const uint4 e2 = make_uint4(p4 | kPriorMark, __float_as_uint(pb.y), p6 | kPriorMark, __float_as_uint(value));
     const bool second = c4::popc32(empty1) > c4::popc32(empty0);
-    Claim r = cache_claim(second ? bk1 : bk0, second ? empty1 : empty0, k0, k1, e1, e2);
-    if (r == kClaimFull && cb.b1 != cb.b0) r = cache_claim(second ? bk0 : bk1, second ? empty0 : empty1, k0, k1, e1, e2);
+    Claim r = cache_claim(second ? bk1 : bk0, second ? empty1 : empty0, k0, k1, e1, e2, C.seq);
+    if (r == kClaimFull && cb.b1 != cb.b0)
+        r = cache_claim(second ? bk0 : bk1, second ? empty0 : empty1, k0, k1, e1, e2, C.seq);
     if (r == kClaimFull) atomicAdd(C.ctr + 1, 1u);
     return r == kClaimDone;
 }
@@ -383,6 +394,8 @@ __device__ __forceinline__ void slot_leaf(const TreeView &T, const BatchView &B,
                 pr[1] = make_float4(__uint_as_float(q2.x & ~kPriorMark), __uint_as_float(q2.y),
                                     __uint_as_float(q2.z & ~kPriorMark), 0.f);
                 B.value[slot] = __uint_as_float(q2.w);
+                // the entry's hit stamp: a plain store, nothing waits for it
+                ((uint32_t *)((match_a ? ea : eb) + 3))[1] = C.seq;
             }
             return;
         }
@@ -601,6 +614,64 @@ __global__ void k_trees_init(TreeView T, RootsOut R, uint32_t first_tree, uint32
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) tree_clear(T, R, first_tree + i);
 }
+
+// ---------------------------------------------------------------- thinning
+// Between search calls (no search kernel runs: cache_thin), a table past its fill
+// threshold is thinned, not emptied: the entries that earned their place stay, at
+// the same generation, and the others are zeroed whole, which leaves their ways
+// empty for cache_claim.  An entry's class is whether a lookup ever accepted it
+// (hit stamp non-zero), its age the search calls since its latest stamp (the hit
+// stamp, else the born stamp), at most kAges - 1.
+//
+// Both passes are grid-stride over the table's 16-B quarters, four lanes per
+// entry (lanes 4k .. 4k + 3 of a wave: coalesced), the claim words taken from
+// the first lane of the four and the stamps from the last.
+struct ThinEntry {
+    bool live;      // claimed (between search calls: complete)
+    uint32_t cls;   // 0 never hit, 1 hit
+    uint32_t age;
+};
+__device__ __forceinline__ ThinEntry thin_entry(const uint4 &q, uint32_t now) {
+    const uint32_t c0 = (uint32_t)__shfl((int)q.x, 0, 4), c1 = (uint32_t)__shfl((int)q.y, 0, 4);
+    const uint32_t born = (uint32_t)__shfl((int)q.x, 3, 4), hit = (uint32_t)__shfl((int)q.y, 3, 4);
+    const uint32_t age = now - (hit ? hit : born);
+    return ThinEntry{(c0 | c1) != 0u, hit ? 1u : 0u, age < EvalCache::kAges - 1 ? age : EvalCache::kAges - 1};
+}
+
+// pass 1: hist[cls * kAges + age] += the live entries of that bin (workgroup bins in
+// LDS, one global atomic per non-empty bin)
+__global__ __launch_bounds__(256) void k_thin_count(const uint4 *__restrict__ tab, size_t quarters, uint32_t now,
+                                                    uint32_t *hist) {
+    __shared__ uint32_t bins[2 * EvalCache::kAges];
+    for (uint32_t b = threadIdx.x; b < 2 * EvalCache::kAges; b += blockDim.x) bins[b] = 0u;
+    __syncthreads();
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < quarters; i += stride) {
+        const ThinEntry te = thin_entry(tab[i], now);
+        if ((i & 3) == 0 && te.live) atomicAdd(&bins[te.cls * EvalCache::kAges + te.age], 1u);
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < 2 * EvalCache::kAges; b += blockDim.x)
+        if (bins[b]) atomicAdd(hist + b, bins[b]);
+}
+
+// pass 2: zero every live entry whose age is at or past its class's cutoff
+// (cut[cls]: 0 drops the class, kAges keeps it), and add the survivors to *live
+// (zeroed before the launch), one atomic per wave
+__global__ __launch_bounds__(256) void k_thin_sweep(uint4 *__restrict__ tab, size_t quarters, uint32_t now,
+                                                    uint32_t cut_fresh, uint32_t cut_hit, uint32_t *live) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    uint32_t kept = 0;   // of this wave (the same in all its lanes that ran the iteration)
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < quarters; i += stride) {
+        const ThinEntry te = thin_entry(tab[i], now);
+        const bool drop = te.live && te.age >= (te.cls ? cut_hit : cut_fresh);
+        if (drop) tab[i] = make_uint4(0u, 0u, 0u, 0u);
+        kept += (uint32_t)c4::popc64(__ballot((i & 3) == 0 && te.live && !drop));
+    }
+    // (the table is a multiple of 32 quarters: a wave's lanes run the same iterations
+    // but for the lanes past the end of a one-bucket table; lane 0 runs them all)
+    if ((threadIdx.x & 63) == 0 && kept) atomicAdd(live, kept);
+}
 }  // namespace
 
 TreeView tree_view(spai_engine *e) {
@@ -621,8 +692,8 @@ static BatchView batch_view(spai_engine *e, int chain, uint32_t it, bool cached)
 
 CacheView cache_view(spai_engine *e) {
     EvalCache &C = e->cache;
-    if (!C.buckets) return CacheView{nullptr, 0u, 0u, nullptr};
-    return CacheView{C.table.p, C.buckets - 1u, C.gen, C.ctr.p};
+    if (!C.buckets) return CacheView{nullptr, 0u, 0u, nullptr, 0u};
+    return CacheView{C.table.p, C.buckets - 1u, C.gen, C.ctr.p, C.seq};
 }
 
 // Empty the table on the engine stream: every search call's chains are joined to it
@@ -640,6 +711,87 @@ int cache_clear(spai_engine *e) {
     C.gen = C.gen % 32767u + 1u;
     C.fill_seen = 0;
     C.clears += 1;
+    return SPAI_OK;
+}
+
+// The ranking of a thinning (kernels: "thinning"): hit entries before never-hit
+// ones, then younger before older, in whole bins of the histogram -- a bin that
+// would cross its budget is dropped whole, so no more than `keep` entries stay.
+// The hit class takes at most kHitShare of `keep` (its youngest bins); what it
+// leaves of `keep`, at least the rest of the share, goes to the newest never-hit
+// entries: on a table small against its traffic the hit entries alone exceed the
+// budget, and without the guard no fresh entry would survive a thinning
+// (scripts/eval_cache_hitrate.py, ThinTable).  cut[cls]: the first age dropped.
+constexpr uint64_t kHitShareNum = 3, kHitShareDen = 4;
+struct ThinCut {
+    uint32_t cut[2];
+    uint64_t kept[2], seen[2];
+};
+static ThinCut thin_cutoff(const uint32_t *hist, uint64_t keep) {
+    ThinCut t{{0u, 0u}, {0, 0}, {0, 0}};
+    for (uint32_t cls = 0; cls < 2; ++cls)
+        for (uint32_t a = 0; a < EvalCache::kAges; ++a) t.seen[cls] += hist[cls * EvalCache::kAges + a];
+    if (t.seen[0] + t.seen[1] <= keep) {   // nothing to evict
+        t.cut[0] = t.cut[1] = EvalCache::kAges;
+        t.kept[0] = t.seen[0];
+        t.kept[1] = t.seen[1];
+        return t;
+    }
+    for (int cls = 1; cls >= 0; --cls) {
+        const uint64_t budget = cls ? keep * kHitShareNum / kHitShareDen : keep - t.kept[1];
+        const uint32_t *h = hist + cls * EvalCache::kAges;
+        while (t.cut[cls] < EvalCache::kAges && t.kept[cls] + h[t.cut[cls]] <= budget) t.kept[cls] += h[t.cut[cls]++];
+    }
+    return t;
+}
+
+// what a thinning at the fill threshold keeps: 1/2 of the capacity
+// (SPAI_EVAL_CACHE_KEEP=<fraction> for A/B measurements)
+uint64_t cache_keep_budget(const EvalCache &C) {
+    const char *v = std::getenv("SPAI_EVAL_CACHE_KEEP");
+    const double f = v ? std::min(1.0, std::max(0.0, std::atof(v))) : 0.5;
+    return (uint64_t)((double)C.entries() * f);
+}
+
+// Thin the table to at most `keep` entries, on the engine stream like cache_clear
+// (no search kernel runs meanwhile).  The generation stays: the survivors are
+// served on.  ctr[0] becomes the survivors' count, so the fill threshold goes by
+// live entries; `inserts` stays "entries ever claimed".  Ages count from the
+// latest search call.  (SPAI_EVAL_CACHE_THIN_LOG=1: one line per thinning on stderr.)
+int cache_thin(spai_engine *e, uint64_t keep) {
+    EvalCache &C = e->cache;
+    if (!C.buckets) return SPAI_OK;
+    hipStream_t st = e->stream;
+    const size_t quarters = C.table.n;
+    int n_cu = 0;
+    SPAI_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, e->device));
+    const uint32_t grid = (uint32_t)std::min<size_t>((quarters + 255) / 256, (size_t)std::max(1, n_cu) * 8);
+    uint32_t *hist = C.ctr.p + 2;
+    uint32_t h[2 * EvalCache::kAges];
+    SPAI_HIP(hipMemsetAsync(hist, 0, sizeof(h), st));
+    k_thin_count<<<grid, 256, 0, st>>>(C.table.p, quarters, C.seq, hist);
+    SPAI_HIP(hipGetLastError());
+    SPAI_HIP(hipMemcpyAsync(h, hist, sizeof(h), hipMemcpyDeviceToHost, st));
+    SPAI_HIP(hipStreamSynchronize(st));
+    const ThinCut t = thin_cutoff(h, keep);
+    const uint64_t seen = t.seen[0] + t.seen[1], kept = t.kept[0] + t.kept[1];
+    if (kept == seen) return SPAI_OK;   // the table holds no more than `keep`: nothing evicted, not a thinning
+    SPAI_HIP(hipMemsetAsync(C.ctr.p, 0, 4, st));
+    k_thin_sweep<<<grid, 256, 0, st>>>(C.table.p, quarters, C.seq, t.cut[0], t.cut[1], C.ctr.p);
+    SPAI_HIP(hipGetLastError());
+    C.inserts_cleared += (double)(seen - kept);
+    C.evicted += (double)(seen - kept);
+    C.kept_hit = (double)t.kept[1];
+    C.fill_seen = (uint32_t)kept;
+    C.thins += 1;
+    C.clears += 1;
+    const char *log = std::getenv("SPAI_EVAL_CACHE_THIN_LOG");
+    if (log && std::atoi(log))
+        std::fprintf(stderr, "eval cache thin %.0f: call %u, keep %llu of %llu live: hit %llu kept %llu (age < %u), "
+                             "never hit %llu kept %llu (age < %u)\n",
+                     C.thins, C.seq, (unsigned long long)keep, (unsigned long long)seen, (unsigned long long)t.seen[1],
+                     (unsigned long long)t.kept[1], t.cut[1], (unsigned long long)t.seen[0],
+                     (unsigned long long)t.kept[0], t.cut[0]);
     return SPAI_OK;
 }
 
@@ -694,7 +846,7 @@ int cache_prepare(spai_engine *e, bool for_net) {
         SPAI_TRY(rc);
         if (buckets) {
             if (!C.ctr.p) {
-                SPAI_TRY(C.ctr.alloc(2));
+                SPAI_TRY(C.ctr.alloc(EvalCache::kCtrWords));
                 SPAI_HIP(hipMemsetAsync(C.ctr.p, 0, 8, e->stream));
             }
             C.buckets = buckets;
@@ -906,6 +1058,8 @@ static int evaluate(const Chain &c, hipStream_t st, const BatchView &bv, uint32_
 int chains_launch(spai_engine *e, const uint32_t *trees, const Chain *chains, int nchain, uint32_t grid_cap, bool timed,
                   bool tail) {
     hipStream_t st = e->stream;
+    // the call's sequence number, from 1: the stamp of the cache entries it claims and hits
+    const uint32_t seq = e->cache.seq = e->cache.seq + 1u ? e->cache.seq + 1u : 1u;
     uint32_t n = 0, iters = 0;
     int conc = 0;   // chains whose forwards share the CUs
     for (int h = 0; h < nchain; ++h) {   // per-iteration leaf counters (also the batch slot counters)
@@ -941,12 +1095,14 @@ int chains_launch(spai_engine *e, const uint32_t *trees, const Chain *chains, in
             if (!c.cnt || it >= c.iters) continue;
             const hipStream_t sh = e->chain_stream[h];
             const BatchView bv = batch_view(e, h, it, c.cache.tab);
+            CacheView cache = c.cache;
+            cache.seq = seq;
             const uint32_t nh = c.cnt, g8 = (nh + kTreesPerBlock - 1) / kTreesPerBlock;
             const uint32_t *act = e->active.p + c.off;
             const bool sample = timed && (it % e->timer.stride == 0);
             if (it == 0) {
                 if (sample) SPAI_TRY(timer_record(e, 0, it, true, sh, h));
-                k_select<false><<<g8, kBlock, 0, sh>>>(tv, bv, c.cache, act, nh, e->cfg.c, e->err.p, 0u);
+                k_select<false><<<g8, kBlock, 0, sh>>>(tv, bv, cache, act, nh, e->cfg.c, e->err.p, 0u);
                 if (sample) SPAI_TRY(timer_record(e, 0, it, false, sh, h));
             }
             if (sample) SPAI_TRY(timer_record(e, 1, it, true, sh, h));
@@ -955,12 +1111,12 @@ int chains_launch(spai_engine *e, const uint32_t *trees, const Chain *chains, in
             if (it + 1 < c.iters) {
                 const bool s2 = timed && ((it + 1) % e->timer.stride == 0);
                 if (s2) SPAI_TRY(timer_record(e, 0, it + 1, true, sh, h));
-                k_expand_select<false><<<g8, kBlock, 0, sh>>>(tv, bv, batch_view(e, h, it + 1, c.cache.tab), c.cache,
+                k_expand_select<false><<<g8, kBlock, 0, sh>>>(tv, bv, batch_view(e, h, it + 1, c.cache.tab), cache,
                                                               act, nh, e->cfg.c, e->err.p, 0u);
                 if (s2) SPAI_TRY(timer_record(e, 0, it + 1, false, sh, h));
             } else {
                 if (sample) SPAI_TRY(timer_record(e, 2, it, true, sh, h));
-                k_expand<<<g8, kBlock, 0, sh>>>(tv, bv, c.cache, nh, e->err.p);
+                k_expand<<<g8, kBlock, 0, sh>>>(tv, bv, cache, nh, e->err.p);
                 if (sample) SPAI_TRY(timer_record(e, 2, it, false, sh, h));
             }
         }
@@ -980,10 +1136,11 @@ int chains_launch(spai_engine *e, const uint32_t *trees, const Chain *chains, in
 int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, SearchRun &R) {
     const int kind = (int)e->cfg.eval;
     hipStream_t st = e->stream;
-    // evaluation cache: allocated on first use; emptied here, between search calls
-    // (no chain runs), once it is more than 7/8 full, so a long stream keeps hitting
+    // evaluation cache: allocated on first use; thinned here, between search calls
+    // (no chain runs), once it is more than 7/8 full: the entries that were hit and
+    // the newest stay, so a long stream keeps hitting what it was hitting
     SPAI_TRY(cache_prepare(e, kind == SPAI_EVAL_NET));
-    if (cache_nearly_full(e->cache)) SPAI_TRY(cache_clear(e));
+    if (cache_nearly_full(e->cache)) SPAI_TRY(cache_thin(e, cache_keep_budget(e->cache)));
     // tail mode (select_tree RUN_ON, one chain): late in a game, when in the previous
     // search call of these trees no tree evaluated SPAI_TAIL_TREE_EVALS leaves or
     // more (a pass per live leaf of the busiest tree: few passes), or the call
@@ -1007,12 +1164,13 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
     // chain h searches an even share of the trees, in order
     const ChainPolicy pol = tail ? ChainPolicy{1, 0u} : chains_for(n, e->last_evals_per_iter);
     const int nchain = R.nchain = pol.chains;
-    const CacheView cv = cache_view(e);
+    CacheView cv = cache_view(e);
     for (int h = 0; h < nchain; ++h) {
         const uint32_t off = (uint32_t)((uint64_t)n * h / nchain);
         R.chain[h] = Chain{off, (uint32_t)((uint64_t)n * (h + 1) / nchain) - off, num_searches, kind, e->net, cv};
     }
     SPAI_TRY(chains_launch(e, tree_idx, R.chain, nchain, pol.grid_cap, true, tail));
+    cv.seq = e->cache.seq;   // (the tail passes below are this call's too)
     R.n_counts = num_searches;   // leaf counters to read back per chain
     if (tail) {
         // passes on the engine stream: select(0), then per pass p: evaluate(p),
@@ -1231,6 +1389,8 @@ int eval_cache_set_capacity(spai_engine *e, uint64_t entries) {
 
 int eval_cache_clear(spai_engine *e) { return cache_clear(e); }
 
+int eval_cache_thin(spai_engine *e, uint64_t keep_entries) { return cache_thin(e, keep_entries); }
+
 int eval_cache_stats(spai_engine *e, spai_eval_cache_stats *out) {
     EvalCache &C = e->cache;
     uint32_t ctr[2] = {0, 0};
@@ -1242,6 +1402,10 @@ int eval_cache_stats(spai_engine *e, spai_eval_cache_stats *out) {
     out->dropped = ctr[1];
     out->clears = C.clears;
     out->capacity = (double)C.entries();
+    out->thins = C.thins;
+    out->evicted = C.evicted;
+    out->live = C.buckets ? (double)ctr[0] : 0.0;
+    out->kept_hit = C.kept_hit;
     return SPAI_OK;
 }
 

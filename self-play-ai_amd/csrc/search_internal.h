@@ -39,7 +39,8 @@ struct CacheView {
     uint4 *tab;      // null: off
     uint32_t mask;   // buckets - 1
     uint32_t gen;
-    uint32_t *ctr;   // [0] entries claimed since the clear, [1] dropped inserts
+    uint32_t *ctr;   // [0] live entries (claims since the clear or thinning + its survivors), [1] dropped inserts
+    uint32_t seq;    // the search call's sequence number (chains_launch): what the entries' stamps are written with
 };
 
 struct RootsOut {
@@ -166,7 +167,11 @@ inline RootsOut roots_out(spai_engine *e) {
 }
 int cache_prepare(spai_engine *e, bool for_net);
 int cache_clear(spai_engine *e);
-// more than 7/8 full: time to empty it, between search calls (with two candidate buckets per
+// Thin the table, between search calls, to at most keep_entries by the ranking of search.hip
+// "thinning"; the generation stays, so the survivors stay valid.
+int cache_thin(spai_engine *e, uint64_t keep_entries);
+uint64_t cache_keep_budget(const EvalCache &C);   // what a thinning at the fill threshold keeps
+// more than 7/8 full: time to thin it (a match: to empty it), between search calls (with two candidate buckets per
 // position 0.4 % of the inserts find both full at that load; one bucket lost 7 % at 3/4)
 inline bool cache_nearly_full(const EvalCache &C) { return C.buckets && (uint64_t)C.fill_seen * 8 > C.entries() * 7; }
 // a call's leaves: `served` live ones, `forwarded` of them through the net; the table's fill after it

@@ -127,13 +127,15 @@ struct Batch {
 // Evaluation cache of the Connect4 search (search.hip "evaluation cache"): a hash
 // table in HBM from the full leaf position (mine, theirs) to the evaluator's 7
 // masked priors and value, valid for one weight set.  8-way buckets of 64-B
-// entries; insert-only between clears.
+// entries; insert-only between clears and thinnings.
 struct EvalCache {
     static constexpr uint32_t kWays = 8;
     static constexpr uint64_t kEntriesPerTree = 16384;    // default capacity per tree slot (cfg.max_trees): 1 MiB
     static constexpr uint64_t kEntryBytes = 64;
     static constexpr uint64_t kDefaultDeviceShare = 16;   // the default takes at most 1/16 of the device's total memory
     static constexpr uint32_t kMinDefaultBuckets = 1024;  // a default table that does not fit is halved down to this
+    static constexpr uint32_t kAges = 256;                // a thinning's histogram: [never hit | hit] x age in search calls
+    static constexpr uint32_t kCtrWords = 2 + 2 * kAges;  // ctr: the two counters, then the histogram
     bool user_set = false;          // capacity set through spai_eval_cache_set_capacity (else SPAI_EVAL_CACHE / default)
     uint64_t requested = 0;         // user_set: entries asked for (0: off)
     bool ready = false;             // capacity resolved and the table allocated (or the cache off)
@@ -141,9 +143,11 @@ struct EvalCache {
     uint32_t buckets = 0;           // power of two; 0: off
     uint32_t gen = 0;               // weight/epoch generation in the key words' spare bits, 1..32767
     DevBuf<uint4> table;            // [buckets][kWays][4]
-    DevBuf<uint32_t> ctr;           // [0] entries claimed since the last clear, [1] inserts dropped (ever)
+    DevBuf<uint32_t> ctr;           // [0] live entries, [1] inserts dropped (ever), [2..] a thinning's histogram
+    uint32_t seq = 0;               // sequence number of the latest search call (chains_launch), from 1
     uint32_t fill_seen = 0;         // ctr[0] as of the end of the latest search call
     double lookups = 0, hits = 0, inserts_cleared = 0, clears = 0;   // host totals (inserts: + ctr[0])
+    double thins = 0, evicted = 0, kept_hit = 0;                      // thinnings (also counted in clears)
     uint64_t entries() const { return (uint64_t)buckets * kWays; }
 };
 
@@ -358,6 +362,7 @@ int selfplay_run(spai_engine *e, uint32_t n_games, uint64_t gid_base, spai_sampl
 // clear it (weights changed: always with a new generation); counters
 int eval_cache_set_capacity(spai_engine *e, uint64_t entries);
 int eval_cache_clear(spai_engine *e);
+int eval_cache_thin(spai_engine *e, uint64_t keep_entries);
 int eval_cache_stats(spai_engine *e, spai_eval_cache_stats *out);
 // match.hip
 int match_run(spai_engine *e, const spai_match_player *a, const spai_match_player *b, uint32_t n_games,

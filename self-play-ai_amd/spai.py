@@ -33,6 +33,7 @@ SYMBOLS = [
     "spai_net_destroy", "spai_net_forward", "spai_predict", "spai_engine_set_net", "spai_trees_create",
     "spai_tree_reset", "spai_search", "spai_tree_use_subtree", "spai_tree_node", "spai_tree_child_stats", "spai_tree_size",
     "spai_selfplay_run", "spai_selfplay_stream", "spai_eval_cache_set_capacity", "spai_eval_cache_get_stats",
+    "spai_eval_cache_thin",
     "spai_match_config_default", "spai_match_run",
     "spai_engine_set_timing", "spai_engine_timing", "spai_engine_timing_items",
     "spai_net_phase_cycles", "spai_net_bench", "spai_net_bench_conc", "spai_adam_config_default", "spai_learner_create", "spai_learner_destroy",
@@ -93,7 +94,8 @@ class SelfPlayStats(C.Structure):
 
 
 class EvalCacheStats(C.Structure):
-    _fields_ = [(k, C.c_double) for k in ("lookups", "hits", "inserts", "dropped", "clears", "capacity")]
+    _fields_ = [(k, C.c_double) for k in ("lookups", "hits", "inserts", "dropped", "clears", "capacity",
+                                          "thins", "evicted", "live", "kept_hit")]
 
 
 class MatchPlayer(C.Structure):
@@ -200,6 +202,7 @@ def lib():
         L.spai_selfplay_stream.argtypes = [vp, u32, u32, u64, SINK, vp, P(SelfPlayStats)]
         L.spai_eval_cache_set_capacity.argtypes = [vp, u64]
         L.spai_eval_cache_get_stats.argtypes = [vp, P(EvalCacheStats)]
+        L.spai_eval_cache_thin.argtypes = [vp, u64]
         L.spai_match_config_default.argtypes = [P(MatchConfig)]
         L.spai_match_run.argtypes = [vp, P(MatchPlayer), P(MatchPlayer), u32, u64, P(MatchConfig), P(MatchGame),
                                      P(MatchStats)]
@@ -521,6 +524,11 @@ class Engine:
         st = EvalCacheStats()
         _check(lib().spai_eval_cache_get_stats(self.h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in EvalCacheStats._fields_}
+
+    def eval_cache_thin(self, keep_entries):
+        """thin the table now to at most keep_entries (hit entries first, then the newest; the
+        survivors stay valid); 0 empties it"""
+        _check(lib().spai_eval_cache_thin(self.h, int(keep_entries)))
 
     # ---- profiling
     def set_timing(self, on, stride=None):
