@@ -135,6 +135,18 @@ int spai_net_forward(spai_net *net, uint32_t n, const float *x, float *logits, f
 int spai_predict(spai_net *net, uint32_t n, const spai_c4_state *states, float *priors, float *values);
 /* Evaluator that search uses when cfg.eval == SPAI_EVAL_NET (Mcts.model, mcts.rs:41-44) */
 int spai_engine_set_net(spai_engine *eng, spai_net *net);
+/* Weight refresh in place (either dtype): afterwards `net` is indistinguishable
+ * from spai_net_create(eng, blocks, 64, params, n, dtype) -- same allocations,
+ * same handle, every packed word equal (the BatchNorm fold and the fragment pack
+ * run as a HIP kernel that restates spai_net_create's host packing; the array is
+ * uploaded to a staging buffer the net allocates at the first call and keeps).
+ * Runs on the engine's stream, behind every search that still reads the old
+ * weights; returns once the new ones are in place.  If `net` is the engine's
+ * current net the evaluation cache is cleared with a new generation, as by
+ * spai_engine_set_net; another net leaves the cache alone.  A wrong n_params is
+ * SPAI_ERR_INVALID and leaves the weights as they were.
+ * (From a learner's device parameters: spai_net_set_params_from_learner.) */
+int spai_net_set_params(spai_net *net, const float *params, size_t n_params);
 
 /* ------------------------------------------------------------------ policy
  * Policy trait methods (game/mod.rs:35-44) on a flat policy array (Connect4 7,
@@ -400,6 +412,14 @@ int spai_learner_train(spai_learner *l, uint32_t n, const float *states, const f
  * (after the cross-rank reduction, before the 1/world scale), flat order */
 int spai_learner_params(spai_learner *l, float *params, size_t n_params);
 int spai_learner_grads(spai_learner *l, float *grads, size_t n_params);
+/* spai_net_set_params from the learner's current device parameters, with no
+ * host copy: the same kernel reads them in place, stream-ordered behind the
+ * learner's latest step (learner and net share the engine's stream), so the next
+ * call on the engine sees the new weights; bit-identical to
+ * spai_net_set_params(net, <spai_learner_params>).  SPAI_ERR_INVALID, with the
+ * mismatch named and the weights untouched, when the learner has another
+ * blocks or hidden than the net or belongs to another engine. */
+int spai_net_set_params_from_learner(spai_net *net, spai_learner *l);
 /* the last train step's post-ReLU activations of conv layer `layer` (stem, the
  * 2*blocks residual convs, policy head, value head), [B][co][6][7]: the ReLU
  * masks the step took, for checking gradients against a float64 restatement */

@@ -218,6 +218,8 @@ extern "C" {
     pub fn spai_predict(net: *mut spai_net, n: u32, states: *const spai_c4_state, priors: *mut f32,
                         values: *mut f32) -> c_int;
     pub fn spai_engine_set_net(e: *mut spai_engine, net: *mut spai_net) -> c_int;
+    pub fn spai_net_set_params(net: *mut spai_net, params: *const f32, n_params: usize) -> c_int;
+    pub fn spai_net_set_params_from_learner(net: *mut spai_net, l: *mut spai_learner) -> c_int;
 
     // Tree + Mcts::search (mcts.rs:32-39,67-89,161-192,196-332)
     pub fn spai_trees_create(e: *mut spai_engine, n: u32) -> c_int;

@@ -326,6 +326,20 @@ int spai_engine_set_net(spai_engine *e, spai_net *n) {
     return eval_cache_clear(e);   // cached evaluations belong to the previous weights
 }
 
+int spai_net_set_params(spai_net *n, const float *params, size_t n_params) {
+    SPAI_PTR(n);
+    SPAI_PTR(params);
+    ENG_CHECK(n->eng);
+    return net_set_params(n, params, n_params);
+}
+
+int spai_net_set_params_from_learner(spai_net *n, spai_learner *l) {
+    SPAI_PTR(n);
+    SPAI_PTR(l);
+    ENG_CHECK(n->eng);
+    return net_set_params_from_learner(n, l);
+}
+
 int spai_eval_cache_set_capacity(spai_engine *e, uint64_t entries) {
     ENG_CHECK(e);
     return eval_cache_set_capacity(e, entries);

@@ -28,10 +28,13 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "net_c4_layout.h"
 #include "spai_internal.h"
 
 namespace spai {
 namespace {
+
+using namespace c4net;   // kHid, the k-step counts, the head and fused-linear shapes
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -39,7 +42,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef short i16x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kHid = 64;
 constexpr int kS = 8;                      // max positions per workgroup group
 constexpr int kP = kS * c4::kCells;        // 336 board cells (LDS rows) at S = 8
 // position tiles (16 LDS rows each) for a group of S positions
@@ -52,37 +54,18 @@ constexpr int kWaves = 4;                  // plan waves: the work split of ever
 // the tasks; the stem, head and linear run on waves 0-3.  Group sizes <= 5 only
 // (the partial-sum buffer must fit beside the activations).
 constexpr int kThreads = kWaves * 64;
-constexpr int kKStepsRes = 18;             // 576 / 32
-constexpr int kHeadC = 35;                 // 32 policy + 3 value channels
-constexpr int kPolIn = 32 * c4::kCells;    // 1344
-constexpr int kValIn = 3 * c4::kCells;     // 126
 
 // LDS carve (bytes)
 constexpr int kZ = 0;                      // 256 B of zeros just below X (out-of-board taps)
 constexpr int kX = 256;                    // [336][128 B] bf16 activations (256-B aligned)
 constexpr int kZ1 = kX + kP * 128;         // 256 B of zeros just below Y
 constexpr int kY = kZ1 + 256;              // second activation buffer
-// Head features in LDS: H[s][cell*36 + c] (c < 35: 32 policy + 3 value channels,
-// c = 35 is a zero pad), so the head conv's epilogue stores 4 channels of a cell
-// as one 8-B word.  The fused linear runs over this cell-major K order (the host
-// permutes the linear weights from the reference's c*42 + cell flatten to it).
-constexpr int kHC = 36;                    // channels per cell in H
-constexpr int kLinFeat = kHC * 42;         // 1512
-constexpr int kLinK = 1536;                // padded to 48 k-steps of 32
-constexpr int kLinKSteps = kLinK / 32;     // 48
+// (the head features H[s][cell*36 + c] and the fused linear's packed-K layout: net_c4_layout.h)
 constexpr int kLinPitch = kLinK + 16;      // the largest head-feature pitch (lin_pitch) sizes the overlay
-// The fused linear has 8 outputs (7 logits + the value), so an MFMA B fragment
-// of 16 columns would be half zeros.  The two K halves are packed into the 16
-// columns instead: column n = (output n & 7, K half n >> 3), A row m =
-// (position m & 7, K half m >> 3), and the diagonal blocks of D are the two
-// halves' partial sums -- 24 k-steps and 24 KiB of weights, not 48.
-constexpr int kLinHalves = 2;
-constexpr int kLinBSteps = kLinKSteps / kLinHalves;   // B-fragment k-steps (1 KiB each)
 constexpr int kH = kY;                     // bf16 head features [8][kLinPitch] overlay Y
 constexpr int kHBytes = kP * 128;          // (all of Y)
 constexpr int kB = kH + kHBytes;           // 8 x (mine, theirs)
 constexpr int kL = kB + kS * 16;           // linear partials [4 waves][halves][8][8] f32
-constexpr int kMaxBlocks = 20;
 constexpr int kBiasFloats = kHid + 2 * kMaxBlocks * kHid + kHid;   // stem, residual convs, head (64 padded)
 constexpr int kBias = kL + kWaves * kLinHalves * 64 * 4; // all conv biases, staged once per workgroup
 constexpr int kBiasPer = (kBiasFloats + kThreads - 1) / kThreads;   // per thread
@@ -1394,6 +1377,7 @@ void net_destroy(spai_net *n) {
     n->io_count.release();
     n->geo.release();
     n->lane_geo.release();
+    n->stage.release();
     delete n;
 }
 

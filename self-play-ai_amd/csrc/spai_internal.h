@@ -180,6 +180,7 @@ struct spai_net {
     spai::DevBuf<uint32_t> io_count;
     spai::DevBuf<uint32_t> geo;     // LDS row -> cell / neighbour table of the cell orders (net_c4.hip)
     spai::DevBuf<uint32_t> lane_geo;   // per-lane conv geometry of every (group size, plan, wave, tile) (net_c4.hip)
+    spai::DevBuf<float> stage;      // flat fp32 parameters of a host weight refresh (net_c4_pack.hip); allocated by the first
 };
 
 // Device training step of the C4 net (learner.hip).
@@ -308,6 +309,10 @@ int net_eval_batch(spai_net *net, hipStream_t st, const uint32_t *d_count, uint3
 int net_create_f32(spai_net *n, const float *params);
 int net_f32_launch(spai_net *n, hipStream_t st, const uint32_t *d_count, uint32_t max_n, const uint64_t *mine,
                    const uint64_t *theirs, const float *x, float *priors, float *value, float *logits);
+
+// net_c4_pack.hip: weight refresh in place, from a host array or a learner's device parameters
+int net_set_params(spai_net *net, const float *params, size_t nparams);
+int net_set_params_from_learner(spai_net *net, spai_learner *l);
 
 // learner.hip
 int learner_create(spai_engine *e, int blocks, int hidden, const float *params, size_t n, const spai_adam_config *cfg,

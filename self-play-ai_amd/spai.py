@@ -30,7 +30,8 @@ SYMBOLS = [
     "spai_engine_destroy", "spai_engine_sync", "spai_games_resize", "spai_games_reset", "spai_games_write",
     "spai_games_read", "spai_legal_mask", "spai_apply", "spai_value_terminated", "spai_encode",
     "spai_mask_invalid", "spai_rules_bench", "spai_net_num_params", "spai_net_init_params", "spai_net_create",
-    "spai_net_destroy", "spai_net_forward", "spai_predict", "spai_engine_set_net", "spai_trees_create",
+    "spai_net_destroy", "spai_net_forward", "spai_predict", "spai_engine_set_net", "spai_net_set_params",
+    "spai_net_set_params_from_learner", "spai_trees_create",
     "spai_tree_reset", "spai_search", "spai_tree_use_subtree", "spai_tree_node", "spai_tree_child_stats", "spai_tree_size",
     "spai_selfplay_run", "spai_selfplay_stream", "spai_eval_cache_set_capacity", "spai_eval_cache_get_stats",
     "spai_eval_cache_thin",
@@ -191,6 +192,8 @@ def lib():
         L.spai_net_forward.argtypes = [vp, u32, vp, vp, vp]
         L.spai_predict.argtypes = [vp, u32, vp, vp, vp]
         L.spai_engine_set_net.argtypes = [vp, vp]
+        L.spai_net_set_params.argtypes = [vp, vp, C.c_size_t]
+        L.spai_net_set_params_from_learner.argtypes = [vp, vp]
         L.spai_trees_create.argtypes = [vp, u32]
         L.spai_tree_reset.argtypes = [vp, u32, vp]
         L.spai_search.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp]
@@ -331,6 +334,17 @@ class Net:
         v = np.zeros(n, np.float32)
         _check(lib().spai_predict(self.h, n, _p(a), _p(pr), _p(v)))
         return pr, v
+
+    def set_params(self, params_or_learner):
+        """weight refresh in place, bit-identical to a fresh Net of the same parameters:
+        a float32 array (spai_net_set_params), or a Learner, whose device parameters are
+        folded and packed with no host copy (spai_net_set_params_from_learner).  Clears
+        the evaluation cache if this is the engine's current net."""
+        if isinstance(params_or_learner, Learner):
+            _check(lib().spai_net_set_params_from_learner(self.h, params_or_learner.h))
+        else:
+            p = np.ascontiguousarray(params_or_learner, np.float32)
+            _check(lib().spai_net_set_params(self.h, _p(p), p.size))
 
 
 class Engine:
@@ -703,6 +717,43 @@ def load_params(path, blocks, hidden=64, game=GAME_CONNECT4, n=None):
     out = np.zeros(num_params(blocks, hidden, game) if n is None else n, np.float32)
     _check(lib().spai_params_load_safetensors(game, blocks, hidden, os.fsencode(path), _p(out), len(out)))
     return out
+
+
+def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_games=100, batch_size=32, num_epochs=4,
+          num_searches=600, temperature=1.25, c=2.0, blocks=6, seed=0, checkpoint_dir=".", clone_self_play=True,
+          params=None, device=0, on_train_set=None, window=None, dtype=None, refresh="device", on_phase=None):
+    """Learner::learn (learner.rs:98-196) for Connect4, with mcts.rs:46-59's defaults:
+    per iteration i, self-play with the current weights on one Engine (the net
+    refreshed in place), Model::train on the samples, checkpoint i.safetensors
+    (save_params).  spai_ttt.learn's loop (spai_learn.learn_loop): the same
+    per-iteration seed rule and the same clone_self_play meaning (the reference
+    clones the self-play state into every self-play iteration, learner.rs:127-137,
+    so True plays one batch of num_parallel_self_play_games games and repeats its
+    samples num_self_play_iters times; False plays that many distinct batches).
+
+    window: stream self-play through that many tree slots (Engine.self_play(window=));
+    the games, and so the checkpoints, are the lockstep ones.  dtype: the self-play
+    net's (DTYPE_BF16 default, DTYPE_F32).  refresh: how the learner's weights reach
+    the self-play net -- "device": Net.set_params(learner), folded and packed by a
+    HIP kernel from the learner's device parameters; "host": Net.set_params(
+    learner.params()), the same kernel behind a host round trip.  Both give the same
+    bits.  on_train_set(i, states, policies, values, game_ids) sees every training
+    set; on_phase(i, name, seconds) the host time of each phase (learn_loop).
+    Returns per-iteration records: samples, loss [total, policy, value] of the last
+    step, games, checkpoint."""
+    if refresh not in ("device", "host"):
+        raise ValueError(f'refresh must be "device" or "host", got {refresh!r}')
+    if dtype not in (None, DTYPE_BF16, DTYPE_F32):
+        raise ValueError(f"dtype must be DTYPE_BF16 or DTYPE_F32, got {dtype!r}")
+    from spai_learn import learn_loop
+    return learn_loop(
+        lambda: Engine(num_searches=num_searches, max_trees=num_parallel_self_play_games, eval_kind=EVAL_NET,
+                       device=device, c=c, temperature=temperature, seed=seed),
+        lambda eng, P: Net(eng, blocks, P, dtype=dtype), lambda eng, P: Learner(eng, blocks, P),
+        init_params(blocks, seed=seed) if params is None else params, blocks, 64, GAME_CONNECT4, num_learn_iters,
+        num_self_play_iters, num_parallel_self_play_games, batch_size, num_epochs, seed, checkpoint_dir,
+        clone_self_play, on_train_set, self_play_kw=None if window is None else dict(window=window),
+        refresh=(lambda net, L: net.set_params(L)) if refresh == "device" else None, on_phase=on_phase)
 
 
 class Replay:

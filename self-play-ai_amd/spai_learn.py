@@ -1,8 +1,10 @@
 """What the TicTacToe and chess bindings share on the learner side: the ctypes
 wrapper of a device learner (spai_<game>_learner_* in include/spai.h) and the
-Learner::learn loop.  spai_ttt and spai_chess subclass and call these."""
+Learner::learn loop.  spai_ttt and spai_chess subclass and call these; spai.learn
+(Connect4) runs the loop on spai.Engine / Net / Learner."""
 import ctypes as C
 import os
+import time
 
 import numpy as np
 
@@ -97,11 +99,22 @@ def _iter_seed(seed, i):
 
 def learn_loop(make_engine, make_net, make_learner, params, blocks, hidden, game, num_learn_iters,
                num_self_play_iters, num_parallel_self_play_games, batch_size, num_epochs, seed, checkpoint_dir,
-               clone_self_play, on_train_set, self_play_kw=None):
-    """Learner::learn (learner.rs:98-196), the body of spai_ttt.learn and spai_chess.learn
-    (their docstrings say what it does): make_engine() -> the self-play engine,
+               clone_self_play, on_train_set, self_play_kw=None, refresh=None, on_phase=None):
+    """Learner::learn (learner.rs:98-196), the body of spai_ttt.learn, spai_chess.learn and
+    spai.learn (their docstrings say what it does): make_engine() -> the self-play engine,
     make_net(eng, P) and make_learner(eng, P) on it, self_play_kw the keyword
-    arguments of every eng.self_play call, hidden and game what save_params records."""
+    arguments of every eng.self_play call, hidden and game what save_params records.
+    refresh(net, L) brings the learner's weights into the self-play net before every
+    iteration but the first (default: net.set_params(L.params())); on_phase(i, name,
+    seconds) receives the host time of iteration i's "refresh", of each of its "self_play"
+    batches and of its "train"."""
+    if refresh is None:
+        def refresh(net, L):
+            net.set_params(L.params())
+
+    def phase(i, name, t0):
+        if on_phase is not None:
+            on_phase(i, name, time.perf_counter() - t0)
     P = np.ascontiguousarray(params, np.float32)
     G = num_parallel_self_play_games
     eng = make_engine()
@@ -113,22 +126,28 @@ def learn_loop(make_engine, make_net, make_learner, params, blocks, hidden, game
     try:
         for i in range(num_learn_iters):
             if i:
-                net.set_params(L.params())
+                t0 = time.perf_counter()
+                refresh(net, L)
+                phase(i, "refresh", t0)
             batches = 1 if clone_self_play else num_self_play_iters
             parts, gids, n_games = [], [], 0
             for b in range(batches):
                 base = (i * num_self_play_iters + b) * G
+                t0 = time.perf_counter()
                 games, _ = eng.self_play(G, game_id_base=base, **(self_play_kw or {}))
+                phase(i, "self_play", t0)
                 n_games += len(games)
                 parts.append(_samples(games))
-                gids.append(np.concatenate([np.full(g["n"], g["game"], np.int64)
+                gids.append(np.concatenate([np.full(len(g["value"]), g["game"], np.int64)
                                             for g in sorted(games, key=lambda g: g["game"])]))
             if clone_self_play:
                 parts, gids = parts * num_self_play_iters, gids * num_self_play_iters
             s, p, v = (np.concatenate([q[k] for q in parts]) for k in range(3))
             if on_train_set is not None:
                 on_train_set(i, s, p, v, np.concatenate(gids))
+            t0 = time.perf_counter()
             loss = L.train(s, p, v, epochs=num_epochs, batch=batch_size, seed=_iter_seed(seed, i))
+            phase(i, "train", t0)
             path = os.path.join(checkpoint_dir, f"{i}.safetensors")
             spai.save_params(path, L.params(), blocks, hidden, game=game)   # spai_params_save_safetensors
             out.append(dict(iteration=i, samples=int(len(v)), loss=[float(x) for x in loss], games=n_games,
