@@ -707,11 +707,28 @@ int spai_chess_selfplay_stream(spai_chess *e, uint32_t n_games, uint32_t window,
 int spai_chess_set_timing(spai_chess *e, int enabled);
 int spai_chess_timing(spai_chess *e, double *avg_ms, double *launches, double *items);
 
-/* weight refresh of a self-play net of either dtype in place (the host packing of
- * spai_chess_net_create / _create_dtype into the same allocations, stream-ordered behind any
- * search still reading the old weights): forward afterwards is bit-identical to
- * a net freshly created from the same parameters */
+/* weight refresh of a self-play net of either dtype in place: the array is uploaded to a
+ * staging buffer the net owns (allocated by the first call) and HIP kernels restate the
+ * host packing of spai_chess_net_create / _create_dtype into the same allocations
+ * (BatchNorm folded in double and bf16 fragments, or the fp32 net's layout), on the
+ * engine's stream behind any search still reading the old weights.  Every packed word
+ * (spai_chess_net_image), and so forward afterwards, is bit-identical to a net freshly
+ * created from the same parameters; padded lanes are rewritten as zero every time.
+ * NaN parameters are outside that claim (sign and payload).  Returns once the weights
+ * are in place: `params` is the caller's again.  A wrong n_params is SPAI_ERR_INVALID
+ * with the weights untouched.  (From a learner's device parameters:
+ * spai_chess_net_set_params_from_learner.) */
 int spai_chess_net_set_params(spai_chess_net *net, const float *params, size_t n_params);
+/* The checker's window on a net's packed weights: drains the engine's stream and copies
+ * the net's weight buffers to `out` back to back, in this order:
+ *   bf16 net  w_stem, w_res, w_p1, w_p2 (bf16 MFMA A fragments [ks = tap*CB + cb][ct]
+ *             [lane 64][8], BatchNorm folded), then fp32 b_stem, b_res, b_p1, b_p2 (80:
+ *             73 biases and 7 zeros), v_w, v_b, l1_w, l1_b, l2_w, l2_b; at blocks = 0
+ *             w_res and b_res are placeholders of 8 and 4 zero elements;
+ *   fp32 net  wf, the one fp32 buffer of spai_chess_net_create_dtype's layout.
+ * *bytes = the image's size; out == NULL only reports it; cap < *bytes is
+ * SPAI_ERR_INVALID.  Two nets whose images are equal compute the same function. */
+int spai_chess_net_image(spai_chess_net *net, void *out, size_t cap, size_t *bytes);
 
 /* Device train step of the chess net (model/chess.rs:48-70 under
  * model/mod.rs:128-141) in exact fp32 (f32 MFMA), on the engine's device and
@@ -763,6 +780,19 @@ int spai_chess_learner_get_compute(spai_chess_learner *l, int *dtype);
 int spai_chess_learner_set_capture(spai_chess_learner *l, int on);
 int spai_chess_learner_gradient(spai_chess_learner *l, int layer, float *out, size_t n);
 int spai_chess_learner_logits(spai_chess_learner *l, float *out, size_t n);
+/* spai_chess_net_set_params from the learner's current device parameters, with no host
+ * copy and no host synchronisation: the same kernels read them in place on the engine's
+ * stream, behind the learner's latest step and behind every search still reading the old
+ * weights, and the call returns once enqueued; the next call on the engine sees the new
+ * weights.  The net holds a snapshot, not an alias: later train steps do not change it.
+ * Bit-identical to spai_chess_net_set_params(net, <spai_chess_learner_params>), for
+ * either net dtype and either learner compute type (the master parameters are fp32).
+ * (A match's second chain runs on a stream of its own, which spai_chess_match_run
+ * drains before it returns, so a refresh after a match needs no further ordering.)
+ * SPAI_ERR_INVALID before anything is launched, with the mismatch named and the weights
+ * untouched, when the learner belongs to another engine, has another block count or
+ * holds another number of parameters than the net needs. */
+int spai_chess_net_set_params_from_learner(spai_chess_net *net, spai_chess_learner *l);
 
 /* ------------------------------------------------------------ chess match
  * play() (main.rs:54-135, whose commented-out lines are the chess variant) with

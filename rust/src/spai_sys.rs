@@ -191,6 +191,7 @@ pub enum spai_ttt {}
 pub enum spai_ttt_net {}
 pub enum spai_chess {}
 pub enum spai_chess_net {}
+pub enum spai_chess_learner {}
 
 pub type spai_sample_sink = extern "C" fn(
     user: *mut c_void,
@@ -269,6 +270,12 @@ extern "C" {
     pub fn spai_chess_net_forward(net: *mut spai_chess_net, n: u32, x: *const f32, logits: *mut f32, value: *mut f32)
         -> c_int;
     pub fn spai_chess_set_net(e: *mut spai_chess, net: *mut spai_chess_net) -> c_int;
+    /// weight refresh in place, packed on the device: from a host array (returns when in place) ...
+    pub fn spai_chess_net_set_params(net: *mut spai_chess_net, params: *const f32, n_params: usize) -> c_int;
+    /// ... or from a chess learner's device parameters (no host copy; returns once enqueued)
+    pub fn spai_chess_net_set_params_from_learner(net: *mut spai_chess_net, l: *mut spai_chess_learner) -> c_int;
+    /// the packed weight buffers in spai.h's order; out NULL only reports *bytes
+    pub fn spai_chess_net_image(net: *mut spai_chess_net, out: *mut c_void, cap: usize, bytes: *mut usize) -> c_int;
     pub fn spai_chess_trees_create(e: *mut spai_chess, n: u32) -> c_int;
     pub fn spai_chess_tree_reset(e: *mut spai_chess, tree: u32, slot: u32) -> c_int;
     pub fn spai_chess_search(e: *mut spai_chess, n: u32, tree_idx: *const u32, num_searches: u32, policy: *mut f32,

@@ -11,6 +11,19 @@
             at all): 1.19 TFLOP at 20 blocks, B = 128.  --compute bf16 measures the
             mixed-precision step and also gives the fraction of the 2.5 PF bf16
             MFMA peak.
+            Then the refresh section (--sections picks step, refresh or both), for the
+            bf16 net at 10 and 20 blocks, in one process, the three routes that bring a
+            learner's weights into the engine's self-play net, alternated --reps times
+            each after a warm-up (host time up to an engine sync, so the device work is
+            counted):
+              device   ChessNet.set_params(L): the device pack on the learner's parameters
+              host     ChessNet.set_params(array): upload + the same device pack
+              parent   L.params(), a fresh ChessNet (the host packer), set_net, the old
+                       net closed -- what the learn loop did before the device pack
+            median and spread in ms, the GB/s the device route reaches against one read
+            of the parameters plus one write of the packed image, and one spai_chess.learn
+            of two iterations with iteration 1's seconds by phase.  This section goes to
+            --refresh-out (default profiles/chess_refresh/record.json).
   --learn   spai_chess.learn() at a small configuration: the loss per iteration
             (--compute f32|bf16: the train step's compute type).
 
@@ -99,6 +112,76 @@ def bench(args):
     return rec
 
 
+def _spread(ms):
+    a = np.sort(np.asarray(ms, np.float64))
+    return dict(n=len(a), median=float(np.median(a)), min=float(a[0]), max=float(a[-1]),
+                q25=float(np.percentile(a, 25)), q75=float(np.percentile(a, 75)))
+
+
+def refresh_bench(args):
+    import spai_chess as sc
+    out = {}
+    rng = np.random.default_rng(0)
+    x = (rng.random((8, 19 * 64)) < 0.3).astype(np.float32)
+    pi = rng.dirichlet(np.ones(64), 8).astype(np.float32)
+    pi = np.concatenate([pi, np.zeros((8, sc.POLICY - 64), np.float32)], 1)
+    z = rng.choice([-1.0, 0.0, 1.0], 8).astype(np.float32)
+    for blocks in (10, 20):
+        eng = sc.ChessEngine(num_searches=1, max_trees=1, max_moves=64)
+        p0 = sc.init_params(blocks, 0)
+        eng.set_net(sc.ChessNet(eng, blocks, p0))
+        L = sc.ChessLearner(eng, blocks, p0)
+        L.train_batch(x, pi, z)
+        P = L.params()
+        sync = lambda: sc._check(sc.lib().spai_chess_sync(eng.h))   # noqa: E731
+
+        def parent():
+            old = eng.net
+            eng.set_net(sc.ChessNet(eng, blocks, L.params()))
+            old.close()
+
+        routes = dict(device=lambda: eng.net.set_params(L), host=lambda: eng.net.set_params(P), parent=parent)
+        times = {k: [] for k in routes}
+        for rep in range(args.refresh_warmup + args.reps):
+            for name, fn in routes.items():
+                sync()
+                t0 = time.perf_counter()
+                fn()
+                sync()
+                if rep >= args.refresh_warmup:
+                    times[name].append((time.perf_counter() - t0) * 1e3)
+        read_b, write_b = 4 * P.size, int(eng.net.image().size)
+        L.close()
+        eng.close()
+        r = {k: _spread(v) for k, v in times.items()}
+        gbs = (read_b + write_b) / (r["device"]["median"] * 1e-3) / 1e9
+        for k, v in r.items():
+            print(f"{blocks} blocks, refresh {k:>7}: median {v['median']:.3f} ms  [{v['min']:.3f}, {v['max']:.3f}]  "
+                  f"n={v['n']}", flush=True)
+        print(f"{blocks} blocks, device route: {read_b / 1e6:.1f} MB read + {write_b / 1e6:.1f} MB written at "
+              f"{gbs:.0f} GB/s; parent / device = {r['parent']['median'] / r['device']['median']:.0f}x", flush=True)
+        out[f"{blocks}x256"] = dict(refresh=r, bytes_read=read_b, bytes_written=write_b, device_gb_per_s=gbs,
+                                    parent_over_device=r["parent"]["median"] / r["device"]["median"])
+    cfg = dict(num_learn_iters=2, num_self_play_iters=2, num_parallel_self_play_games=8, batch_size=32, num_epochs=1,
+               num_searches=16, blocks=10, seed=0)
+    phases = {}
+
+    def on_phase(i, name, secs):
+        d = phases.setdefault(i, dict(refresh=0.0, self_play=0.0, train=0.0))
+        d[name] += secs
+
+    with tempfile.TemporaryDirectory() as d:
+        t0 = time.perf_counter()
+        rec = sc.learn(checkpoint_dir=d, on_phase=on_phase, **cfg)
+        secs = time.perf_counter() - t0
+    for r in rec:
+        r["checkpoint"] = os.path.basename(r["checkpoint"])
+        r["seconds"] = phases.get(r["iteration"])
+    print(f"learn {cfg}: {secs:.1f} s; iteration 1 seconds {rec[1]['seconds']}", flush=True)
+    return dict(net="bf16", reps=args.reps, warmup=args.refresh_warmup, unit="ms", results=out,
+                learn=dict(config=cfg, refresh="device", seconds=secs, iterations=rec))
+
+
 def learn(args):
     import spai_chess as sc
     cfg = dict(num_learn_iters=args.iters, num_self_play_iters=args.self_play_iters,
@@ -122,6 +205,10 @@ def main():
     ap.add_argument("--bench", action="store_true")
     ap.add_argument("--learn", action="store_true")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "chess_learner", "record.json"))
+    ap.add_argument("--refresh-out", default=os.path.join(REPO, "profiles", "chess_refresh", "record.json"))
+    ap.add_argument("--sections", default="step,refresh", help="--bench: step, refresh or both, comma separated")
+    ap.add_argument("--reps", type=int, default=20, help="--bench refresh: timed refreshes per route (at least 20)")
+    ap.add_argument("--refresh-warmup", type=int, default=2)
     ap.add_argument("--commit", default=None, help="commit hash to record (default: git rev-parse HEAD)")
     ap.add_argument("--tag", default="", help="record under bench_<tag> / learn_<tag>")
     ap.add_argument("--configs", default="10x32,10x128,20x32,20x128", help="--bench: blocks x B, comma separated")
@@ -144,6 +231,11 @@ def main():
     args = ap.parse_args()
     if not (args.bench or args.learn):
         ap.error("give --bench and/or --learn")
+    sections = set(args.sections.split(","))
+    if not sections or sections - {"step", "refresh"}:
+        ap.error("--sections: step, refresh or both")
+    if args.bench and "refresh" in sections and args.reps < 20:
+        ap.error("--reps must be at least 20")
     commit = args.commit
     if commit is None:
         try:
@@ -157,14 +249,20 @@ def main():
             record = json.load(f)
     record["commit"] = commit
     sfx = "_" + args.tag if args.tag else ""
-    if args.bench:
+    if args.bench and "refresh" in sections:
+        os.makedirs(os.path.dirname(os.path.abspath(args.refresh_out)), exist_ok=True)
+        with open(args.refresh_out, "w") as f:
+            json.dump(dict(commit=commit, bench=refresh_bench(args)), f, indent=1)
+            f.write("\n")
+    if args.bench and "step" in sections:
         record["bench" + sfx] = bench(args)
     if args.learn:
         record["learn" + sfx] = learn(args)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(record, f, indent=1)
-        f.write("\n")
+    if args.learn or (args.bench and "step" in sections):
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(record, f, indent=1)
+            f.write("\n")
 
 
 if __name__ == "__main__":

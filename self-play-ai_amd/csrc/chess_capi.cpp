@@ -241,6 +241,13 @@ int spai_chess_net_dtype(spai_chess_net *net, int *dtype) {
     return SPAI_OK;
 }
 
+int spai_chess_net_image(spai_chess_net *net, void *out, size_t cap, size_t *bytes) {
+    SPAI_PTR(net);
+    SPAI_PTR(bytes);
+    CH_CHECK(net->eng);
+    return net_image(net, out, cap, bytes);
+}
+
 int spai_chess_net_destroy(spai_chess_net *net) {
     if (!net) return SPAI_OK;
     (void)hipSetDevice(net->eng->device);

@@ -119,6 +119,7 @@ struct spai_chess_net {
     spai::DevBuf<float> io_logits, io_value;
     spai::DevBuf<uint32_t> io_count;
     uint32_t io_cap = 0;
+    spai::DevBuf<float> stage;     // spai_chess_net_set_params' upload of the flat parameters, allocated by its first call
 };
 
 namespace spai {
@@ -148,7 +149,6 @@ size_t net_num_params(int blocks);
 void net_init_params(int blocks, uint64_t seed, float *params);
 int net_create(spai_chess *e, int blocks, const float *params, size_t n, int dtype, spai_chess_net **out);
 void net_destroy(spai_chess_net *net);
-int net_set_params(spai_chess_net *net, const float *params, size_t n);
 // evaluate `count` (device scalar) positions: a bf16 net reads x [max_n][64][kInCh] bf16,
 // an fp32 net xf [max_n][19][64] fp32 (the other pointer is not read)
 int net_eval(spai_chess_net *net, hipStream_t st, const uint32_t *d_count, uint32_t max_n, const uint16_t *x,
@@ -162,6 +162,11 @@ int net_predict(spai_chess_net *net, uint32_t first, uint32_t n, float *priors, 
 void net_f32_pack(int blocks, const float *params, std::vector<float> &buf);
 int net_f32_launch(spai_chess_net *net, hipStream_t st, const uint32_t *d_count, uint32_t max_n, const float *xf,
                    float *logits, float *value);
+
+// chess_net_pack.hip: the device fold and pack of the flat parameters into a net's own buffers
+int net_set_params(spai_chess_net *net, const float *params, size_t n);            // host array; returns when in place
+int net_set_params_device(spai_chess_net *net, const float *d_params, size_t n);   // device array; returns once enqueued
+int net_image(spai_chess_net *net, void *out, size_t cap, size_t *bytes);
 
 // chess_search.hip
 int trees_create(spai_chess *e, uint32_t n);

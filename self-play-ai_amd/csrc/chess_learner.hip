@@ -1,8 +1,10 @@
 // chess_learner.hip — the train step of the chess net on the device
 // (model/chess.rs:48-70 under model/mod.rs:128-141), in fp32 or with the conv
 // GEMMs' operands in bf16 (spai_chess_learner_set_compute), behind
-// spai_chess_learner_* in include/spai.h; and spai_chess_net_set_params, the
-// in-place weight refresh of a self-play net that Learner::learn needs.
+// spai_chess_learner_* in include/spai.h; and the entry points of the in-place
+// weight refresh of a self-play net that Learner::learn needs,
+// spai_chess_net_set_params and spai_chess_net_set_params_from_learner (the
+// learner's state is private to this file; the kernels are chess_net_pack.hip's).
 //
 // Train-mode forward (BatchNorm batch statistics in the trunk; the heads have no
 // BN), loss = -(log_softmax(p) . pi).sum()/B + mean((v - z)^2), backward, one
@@ -1106,6 +1108,21 @@ int spai_chess_net_set_params(spai_chess_net *net, const float *params, size_t n
     SPAI_PTR(params);
     SPAI_SET_DEVICE(net->eng);
     return net_set_params(net, params, n_params);
+}
+
+int spai_chess_net_set_params_from_learner(spai_chess_net *net, spai_chess_learner *l) {
+    SPAI_PTR(net);
+    SPAI_PTR(l);
+    // a learner steps on its engine's stream, and every engine has a stream of its own
+    SPAI_CHECK(l->device == net->eng->device && l->stream == net->eng->stream, SPAI_ERR_INVALID,
+               "learner belongs to another engine than the net");
+    SPAI_CHECK(l->blocks == net->blocks, SPAI_ERR_INVALID, "learner has %d blocks, the net %d", l->blocks, net->blocks);
+    const size_t want = net_num_params(net->blocks);
+    SPAI_CHECK(l->n_params == want && l->p.n >= want, SPAI_ERR_INVALID, "learner holds %zu params, the net needs %zu",
+               l->n_params, want);
+    SPAI_SET_DEVICE(net->eng);
+    // the pack reads the learner's latest parameters: both are on the engine's stream
+    return net_set_params_device(net, l->p.p, want);
 }
 
 }  // extern "C"

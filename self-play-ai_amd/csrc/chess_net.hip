@@ -656,60 +656,11 @@ int net_create(spai_chess *e, int blocks, const float *params, size_t n, int dty
     return SPAI_OK;
 }
 
-// weight refresh in place: net_create's host fold and pack written into the net's own
-// allocations, stream-ordered behind whatever search still reads the old weights
-int net_set_params(spai_chess_net *net, const float *params, size_t n) {
-    SPAI_CHECK(params && n == net_num_params(net->blocks), SPAI_ERR_INVALID, "expected %zu params, got %zu",
-               net_num_params(net->blocks), n);
-    hipStream_t st = net->eng->stream;
-    if (net->dtype == SPAI_DTYPE_F32) {
-        std::vector<float> buf;
-        net_f32_pack(net->blocks, params, buf);
-        SPAI_CHECK(net->wf.n == buf.size(), SPAI_ERR_INVALID, "net allocation does not match");
-        const hipError_t ce = hipMemcpyAsync(net->wf.p, buf.data(), buf.size() * 4, hipMemcpyHostToDevice, st);
-        const hipError_t se = hipStreamSynchronize(st);   // the host vector dies here
-        SPAI_HIP(ce);
-        SPAI_HIP(se);
-        return SPAI_OK;
-    }
-    Packed K;
-    SPAI_TRY(pack_params(net->blocks, params, n, K));
-    auto put16 = [&](DevBuf<uint16_t> &d, const std::vector<uint16_t> &h) -> int {
-        SPAI_CHECK(d.n == h.size(), SPAI_ERR_INVALID, "net allocation does not match");
-        SPAI_HIP(hipMemcpyAsync(d.p, h.data(), h.size() * 2, hipMemcpyHostToDevice, st));
-        return SPAI_OK;
-    };
-    auto putf = [&](DevBuf<float> &d, const std::vector<float> &h) -> int {
-        SPAI_CHECK(d.n == h.size(), SPAI_ERR_INVALID, "net allocation does not match");
-        SPAI_HIP(hipMemcpyAsync(d.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));
-        return SPAI_OK;
-    };
-    int rc = SPAI_OK;
-    if (rc == SPAI_OK) rc = put16(net->w_stem, K.w_stem);
-    if (rc == SPAI_OK) rc = put16(net->w_res, K.w_res);
-    if (rc == SPAI_OK) rc = put16(net->w_p1, K.w_p1);
-    if (rc == SPAI_OK) rc = put16(net->w_p2, K.w_p2);
-    if (rc == SPAI_OK) rc = putf(net->b_stem, K.b_stem);
-    if (rc == SPAI_OK) rc = putf(net->b_res, K.b_res);
-    if (rc == SPAI_OK) rc = putf(net->b_p1, K.b_p1);
-    if (rc == SPAI_OK) rc = putf(net->b_p2, K.b_p2);
-    if (rc == SPAI_OK) rc = putf(net->v_w, K.v_w);
-    if (rc == SPAI_OK) rc = putf(net->v_b, K.v_b);
-    if (rc == SPAI_OK) rc = putf(net->l1_w, K.l1_w);
-    if (rc == SPAI_OK) rc = putf(net->l1_b, K.l1_b);
-    if (rc == SPAI_OK) rc = putf(net->l2_w, K.l2_w);
-    if (rc == SPAI_OK) rc = putf(net->l2_b, K.l2_b);
-    const hipError_t se = hipStreamSynchronize(st);   // the host vectors die here
-    SPAI_TRY(rc);
-    SPAI_HIP(se);
-    return SPAI_OK;
-}
-
 void net_destroy(spai_chess_net *net) {
     if (!net) return;
     for (auto *d : {&net->w_stem, &net->w_res, &net->w_p1, &net->w_p2, &net->io_x}) d->release();
     for (auto *d : {&net->b_stem, &net->b_res, &net->b_p1, &net->b_p2, &net->v_w, &net->v_b, &net->l1_w, &net->l1_b,
-                    &net->l2_w, &net->l2_b, &net->io_logits, &net->io_value, &net->wf, &net->io_xf})
+                    &net->l2_w, &net->l2_b, &net->io_logits, &net->io_value, &net->wf, &net->io_xf, &net->stage})
         d->release();
     net->io_count.release();
     delete net;

@@ -53,7 +53,8 @@ SYMBOLS = [
     "spai_chess_net_create", "spai_chess_net_create_dtype", "spai_chess_net_dtype", "spai_chess_net_destroy", "spai_chess_net_forward", "spai_chess_predict", "spai_chess_set_net",
     "spai_chess_trees_create", "spai_chess_search", "spai_chess_tree_reset", "spai_chess_tree_use_subtree", "spai_chess_tree_root", "spai_chess_trees_advance",
     "spai_chess_selfplay_run", "spai_chess_selfplay_stream", "spai_chess_set_timing", "spai_chess_timing",
-    "spai_chess_net_set_params", "spai_chess_learner_create", "spai_chess_learner_destroy",
+    "spai_chess_net_set_params", "spai_chess_net_set_params_from_learner", "spai_chess_net_image",
+    "spai_chess_learner_create", "spai_chess_learner_destroy",
     "spai_chess_learner_train_batch", "spai_chess_learner_train", "spai_chess_learner_params",
     "spai_chess_learner_grads", "spai_chess_learner_activation", "spai_chess_learner_last_batch",
     "spai_chess_learner_set_compute", "spai_chess_learner_get_compute", "spai_chess_learner_set_capture",

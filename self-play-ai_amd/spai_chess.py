@@ -93,6 +93,8 @@ def lib():
         L.spai_chess_set_timing.argtypes = [vp, i32]
         L.spai_chess_timing.argtypes = [vp, vp, vp, vp]
         L.spai_chess_net_set_params.argtypes = [vp, vp, C.c_size_t]
+        L.spai_chess_net_set_params_from_learner.argtypes = [vp, vp]
+        L.spai_chess_net_image.argtypes = [vp, vp, C.c_size_t, P(C.c_size_t)]
         L.spai_chess_match_config_default.argtypes = [P(ChessMatchConfig)]
         L.spai_chess_match_run.argtypes = [vp, P(ChessMatchPlayer), P(ChessMatchPlayer), u32, u64,
                                            P(ChessMatchConfig), P(ChessMatchGame), vp, P(ChessMatchStats)]
@@ -438,11 +440,26 @@ class ChessNet:
         _check(lib().spai_chess_predict(self.h, first, n, _p(pr), _p(v)))
         return pr, v
 
-    def set_params(self, params):
-        """weight refresh in place: forward afterwards is bit-identical to a fresh
-        ChessNet of the same parameters"""
-        p = np.ascontiguousarray(params, np.float32)
-        _check(lib().spai_chess_net_set_params(self.h, _p(p), p.size))
+    def set_params(self, params_or_learner):
+        """weight refresh in place, folded and packed by HIP kernels: every packed word
+        (image()), and so forward afterwards, is bit-identical to a fresh ChessNet of the
+        same parameters.  The source is a float32 array (spai_chess_net_set_params), or a
+        ChessLearner, whose device parameters are read in place with no host copy and no
+        host synchronisation (spai_chess_net_set_params_from_learner); the net then holds
+        a snapshot of them."""
+        if isinstance(params_or_learner, ChessLearner):
+            _check(lib().spai_chess_net_set_params_from_learner(self.h, params_or_learner.h))
+        else:
+            p = np.ascontiguousarray(params_or_learner, np.float32)
+            _check(lib().spai_chess_net_set_params(self.h, _p(p), p.size))
+
+    def image(self):
+        """the net's packed weight buffers as a uint8 array, in spai_chess_net_image's order"""
+        n = C.c_size_t()
+        _check(lib().spai_chess_net_image(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint8)
+        _check(lib().spai_chess_net_image(self.h, _p(out), out.size, C.byref(n)))
+        return out
 
 
 class ChessLearner(DeviceLearner):
@@ -502,7 +519,8 @@ class ChessLearner(DeviceLearner):
 
 def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_games=100, batch_size=32, num_epochs=4,
           num_searches=600, temperature=1.25, c=2.0, blocks=10, seed=0, checkpoint_dir=".", clone_self_play=True,
-          params=None, device=0, on_train_set=None, window=None, max_moves=None, compute="f32"):
+          params=None, device=0, on_train_set=None, window=None, max_moves=None, compute="f32", refresh="device",
+          on_phase=None):
     """Learner::learn (learner.rs:98-196) for chess, with mcts.rs:46-59's defaults:
     per iteration i, self-play with the current weights on one ChessEngine (the net
     refreshed in place), Model::train on the samples, checkpoint i.safetensors.
@@ -515,11 +533,18 @@ def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_ga
     window: play each batch through that many tree slots (ChessEngine.self_play).
     on_train_set(i, states, policies, values, game_ids) sees every training set.
     compute: the train step's compute type, "f32" or "bf16" (ChessLearner).
+    refresh: how the learner's weights reach the self-play net -- "device":
+    ChessNet.set_params(learner), folded and packed by HIP kernels from the learner's
+    device parameters; "host": ChessNet.set_params(learner.params()), the same kernels
+    behind a host round trip.  Both give the same bits.  on_phase(i, name, seconds)
+    receives the host time of each phase (learn_loop).
     Returns per-iteration records: samples, loss [total, policy, value] of the last
     step, games, checkpoint."""
     G = num_parallel_self_play_games
     if compute not in ChessLearner.COMPUTE:
         raise ValueError(f"compute {compute!r}: 'f32' or 'bf16'")
+    if refresh not in ("device", "host"):
+        raise ValueError(f'refresh must be "device" or "host", got {refresh!r}')
     return learn_loop(
         lambda: ChessEngine(num_searches=num_searches, max_trees=G if window is None else int(window),
                             eval_kind=EVAL_NET, device=device, c=c, temperature=temperature, seed=seed,
@@ -527,4 +552,5 @@ def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_ga
         lambda eng, P: ChessNet(eng, blocks, P), lambda eng, P: ChessLearner(eng, blocks, P, compute=compute),
         init_params(blocks, seed) if params is None else params, blocks, 256, GAME_CHESS, num_learn_iters,
         num_self_play_iters, G, batch_size, num_epochs, seed, checkpoint_dir, clone_self_play, on_train_set,
-        self_play_kw=dict(window=window))
+        self_play_kw=dict(window=window),
+        refresh=(lambda net, L: net.set_params(L)) if refresh == "device" else None, on_phase=on_phase)
