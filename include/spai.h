@@ -884,6 +884,76 @@ int spai_chess_tree_children(spai_chess *e, uint32_t tree, uint16_t *moves, uint
 int spai_chess_tree_child_stats(spai_chess *e, uint32_t tree, uint16_t *moves, uint32_t *visits, float *value_sums,
                                 float *priors, uint32_t *n);
 
+/* -------------------------------------------------- chess compact samples
+ * A self-play sample as self-play knows it: the searched position, the value, and
+ * the root children's (move, visit count) pairs, instead of the dense [19][8][8]
+ * encoding and [4672] policy row built from them (23,556 bytes a position).  The
+ * children of a set of samples are stored CSR-style in two arrays, child_moves
+ * (move codes, in MoveGen order as the tree stores them) and child_visits (N);
+ * sample i owns entries [first, first + n_children) of both.
+ *
+ * The dense form of a sample is: states = the encoding of `state` with plane 16
+ * = state.reps; policies = zeros with (float)N_k / sum_k (float)N_k at
+ * spai_chess_move_index(state.side, move_k); values = value.
+ *
+ * Every entry point below that takes samples checks them on the host first, before
+ * anything is uploaded or launched, and returns SPAI_ERR_INVALID (the message names
+ * the sample's index and the field; a learner's parameters, moments and step count
+ * are untouched) when
+ *   n_children is outside 1..SPAI_CHESS_MAX_MOVES;
+ *   first + n_children goes past n_children_total;
+ *   the state has not exactly one king per side (spai_chess_games_write's rule);
+ *   state.side > 1;
+ *   a child's policy index falls outside [0, 4672);
+ *   two children of the sample have the same policy index (the moves of a legal
+ *     move list never do);
+ *   the sample's visit counts sum to 0 or to 2^24 or more (below 2^24 every partial
+ *     sum is an exact integer in fp32, so the sum does not depend on its order). */
+typedef struct spai_chess_sample {
+    spai_chess_state state;  /* the searched position; .reps = its repetition count (plane 16), .status ignored */
+    float    value;          /* z, signed for the player to move */
+    uint16_t move;           /* the move played */
+    uint16_t n_children;     /* 1..SPAI_CHESS_MAX_MOVES */
+    uint32_t first;          /* index of its first child in child_moves / child_visits */
+    uint32_t pad;
+} spai_chess_sample;         /* 96 bytes */
+
+/* one finished game: n samples in move order, `first` relative to this call's arrays */
+typedef void (*spai_chess_compact_sink)(void *user, uint32_t game_id, uint32_t n,
+                                        const spai_chess_sample *samples, const uint16_t *child_moves,
+                                        const uint32_t *child_visits, uint32_t n_children_total);
+/* spai_chess_selfplay_run (window == 0 or >= n_games) or spai_chess_selfplay_stream
+ * (otherwise) with the samples handed over compact: the same games, draws, emission
+ * order and stats; spai_chess_samples_expand of a game's samples is, bit for bit,
+ * what the dense sink receives for it. */
+int spai_chess_selfplay_compact(spai_chess *e, uint32_t n_games, uint32_t window, uint64_t game_id_base,
+                                spai_chess_compact_sink sink, void *user, spai_selfplay_stats *stats);
+/* The dense form on the host (needs no device), by the functions the dense sink's
+ * arrays are made with: states [n][19*64], policies [n][4672], values [n]; any of
+ * the three may be NULL. */
+int spai_chess_samples_expand(uint32_t n, const spai_chess_sample *samples, const uint16_t *child_moves,
+                              const uint32_t *child_visits, uint32_t n_children_total, float *states,
+                              float *policies, float *values);
+/* spai_chess_learner_train_batch on the samples' dense form, which a HIP kernel
+ * writes on the learner's device from the uploaded records: bit-identical to
+ * spai_chess_learner_train_batch on spai_chess_samples_expand's arrays. */
+int spai_chess_learner_train_batch_compact(spai_chess_learner *l, uint32_t n, const spai_chess_sample *samples,
+                                           const uint16_t *child_moves, const uint32_t *child_visits,
+                                           uint32_t n_children_total, float *loss);
+/* Model::train over n * repeat virtual samples, virtual sample j being sample j % n
+ * (repeat >= 1): bit-identical to spai_chess_learner_train on the expanded arrays
+ * tiled repeat times (the same permutation, choose_multiple(n * repeat, n * repeat,
+ * seed, 0x7EA1B)), without building them. */
+int spai_chess_learner_train_compact(spai_chess_learner *l, uint32_t n, const spai_chess_sample *samples,
+                                     const uint16_t *child_moves, const uint32_t *child_visits,
+                                     uint32_t n_children_total, uint32_t repeat, uint32_t epochs, uint32_t batch,
+                                     uint64_t seed, float *loss);
+/* The checker's window: the last train step's batch as the step read it on the
+ * device, whichever route brought it there.  states [n][19*64], policies [n][4672],
+ * values [n], any of them NULL; SPAI_ERR_INVALID before the first step or when n is
+ * not the last step's batch size. */
+int spai_chess_learner_batch(spai_chess_learner *l, float *states, float *policies, float *values, uint32_t n);
+
 
 /* ---------------------------------------------------------------- tictactoe
  * game/tictactoe.rs + model/tictactoe.rs (BASELINE config 1) on the device.

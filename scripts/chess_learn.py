@@ -24,8 +24,18 @@
             of the parameters plus one write of the packed image, and one spai_chess.learn
             of two iterations with iteration 1's seconds by phase.  This section goes to
             --refresh-out (default profiles/chess_refresh/record.json).
+            The samples section (--sections samples; not part of the default) measures the
+            compact self-play samples (spai_chess.ChessSamples) against the dense arrays, in
+            one process: bytes per sample over a real self-play run (64 games, 64
+            simulations, 10 blocks); ms per train_batch, dense and compact alternated,
+            --reps timed runs each after 3 warm-up rounds, at 10 x 32 and 20 x 128; the
+            seconds of one train() over the same samples both ways; and the peak host RSS
+            (ru_maxrss) of one spai_chess.learn iteration in each mode, each in a fresh
+            child process.  It goes to --samples-out (default
+            profiles/chess_samples/record.json).
   --learn   spai_chess.learn() at a small configuration: the loss per iteration
-            (--compute f32|bf16: the train step's compute type).
+            (--compute f32|bf16: the train step's compute type; --samples dense|compact:
+            how the samples travel from self-play to the learner).
 
 Both merge their result into --out (default profiles/chess_learner/record.json).
 """
@@ -182,12 +192,110 @@ def refresh_bench(args):
                 learn=dict(config=cfg, refresh="device", seconds=secs, iterations=rec))
 
 
+DENSE_BYTES = (19 * 64 + 4672 + 1) * 4   # a dense sample: encoding, policy row, value
+RSS_CONFIG = dict(num_learn_iters=1, num_self_play_iters=8, num_parallel_self_play_games=16, batch_size=32,
+                  num_epochs=1, num_searches=16, blocks=2, seed=0)
+
+
+def rss_child(mode):
+    """one learn iteration in this (fresh) process; prints its peak RSS"""
+    import resource
+
+    import spai_chess as sc
+    with tempfile.TemporaryDirectory() as d:
+        t0 = time.perf_counter()
+        rec = sc.learn(checkpoint_dir=d, samples=mode, **RSS_CONFIG)
+        secs = time.perf_counter() - t0
+    print(json.dumps(dict(mode=mode, ru_maxrss_kb=resource.getrusage(resource.RUSAGE_SELF).ru_maxrss,
+                          samples=rec[0]["samples"], loss=rec[0]["loss"], seconds=secs)), flush=True)
+
+
+def samples_bench(args):
+    import spai_chess as sc
+    out = {}
+    # ---- bytes per sample over a real self-play run
+    G, sims, blocks = 64, 64, 10
+    eng = sc.ChessEngine(num_searches=sims, max_trees=G, seed=0)
+    eng.set_net(sc.ChessNet(eng, blocks, sc.init_params(blocks, 0)))
+    t0 = time.perf_counter()
+    games, stats = eng.self_play(G, samples="compact")
+    secs = time.perf_counter() - t0
+    eng.close()
+    cs = sc.ChessSamples.concat(g["samples"] for g in games)
+    plies = np.array([g["n"] for g in games])
+    nch = cs.samples["n_children"]
+    out["bytes"] = dict(games=G, num_searches=sims, blocks=blocks, self_play_seconds=secs, samples=cs.n,
+                        plies_per_game=dict(min=int(plies.min()), median=float(np.median(plies)), max=int(plies.max())),
+                        children_per_sample=dict(min=int(nch.min()), mean=float(nch.mean()), max=int(nch.max())),
+                        dense_bytes_per_sample=DENSE_BYTES, compact_bytes_per_sample=cs.nbytes / cs.n,
+                        dense_total_bytes=DENSE_BYTES * cs.n, compact_total_bytes=cs.nbytes,
+                        ratio=DENSE_BYTES * cs.n / cs.nbytes)
+    print(f"{cs.n} samples of {G} games ({secs:.1f} s): dense {DENSE_BYTES} B, compact {cs.nbytes / cs.n:.1f} B a "
+          f"sample, {DENSE_BYTES * cs.n / cs.nbytes:.1f}x; plies {out['bytes']['plies_per_game']}, children "
+          f"{out['bytes']['children_per_sample']}", flush=True)
+    # ---- ms per train_batch, dense against compact, alternated
+    pick = np.random.default_rng(0).permutation(cs.n)
+    eng = sc.ChessEngine(num_searches=1, max_trees=1, max_moves=64)
+    out["train_batch_ms"] = {}
+    for blocks, B in ((10, 32), (20, 128)):
+        q = cs.take(pick[:B])
+        dense = q.expand()
+        L = sc.ChessLearner(eng, blocks, sc.init_params(blocks, 0), compute=args.compute)
+        routes = dict(dense=lambda: L.train_batch(*dense), compact=lambda: L.train_batch(q))
+        times = {k: [] for k in routes}
+        for rep in range(3 + args.reps):
+            for name, fn in routes.items():
+                t0 = time.perf_counter()
+                fn()
+                if rep >= 3:
+                    times[name].append((time.perf_counter() - t0) * 1e3)
+        L.close()
+        r = {k: _spread(v) for k, v in times.items()}
+        spread = r["dense"]["max"] - r["dense"]["min"]
+        r["compact_minus_dense_median"] = r["compact"]["median"] - r["dense"]["median"]
+        r["dense_spread"] = spread
+        r["compact_within_dense_spread"] = bool(r["compact"]["median"] <= r["dense"]["median"] + spread)
+        out["train_batch_ms"][f"{blocks}x{B}"] = r
+        for k in routes:
+            print(f"{blocks}x256 B={B} train_batch {k:>7}: median {r[k]['median']:.3f} ms  [{r[k]['min']:.3f}, "
+                  f"{r[k]['max']:.3f}]  n={r[k]['n']}", flush=True)
+        print(f"{blocks}x256 B={B}: compact - dense = {r['compact_minus_dense_median']:+.3f} ms, dense spread "
+              f"{spread:.3f} ms, within: {r['compact_within_dense_spread']}", flush=True)
+    # ---- one train() over the same samples, both ways
+    n = min(cs.n, args.train_samples)
+    q = cs.take(pick[:n])
+    blocks = 10
+    res = {}
+    for mode in ("dense", "compact"):
+        L = sc.ChessLearner(eng, blocks, sc.init_params(blocks, 0), compute=args.compute)
+        t0 = time.perf_counter()
+        loss = L.train(*q.expand(), epochs=1, batch=32) if mode == "dense" else L.train(q, epochs=1, batch=32)
+        res[mode] = dict(seconds=time.perf_counter() - t0, loss=[float(v) for v in loss])
+        L.close()
+    assert res["dense"]["loss"] == res["compact"]["loss"]
+    out["train_seconds"] = dict(samples=n, blocks=blocks, batch=32, epochs=1, note="dense includes expand() on the host",
+                                **res)
+    print(f"train over {n} samples, {blocks} blocks: dense {res['dense']['seconds']:.2f} s, compact "
+          f"{res['compact']['seconds']:.2f} s", flush=True)
+    eng.close()
+    # ---- peak host RSS of one learn iteration, each mode in a fresh child process
+    out["learn_rss"] = dict(config=RSS_CONFIG)
+    for mode in ("dense", "compact"):
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--rss-child", mode], capture_output=True,
+                           text=True, check=True)
+        out["learn_rss"][mode] = json.loads(r.stdout.strip().splitlines()[-1])
+        print(f"learn, one iteration, {mode}: peak RSS {out['learn_rss'][mode]['ru_maxrss_kb'] / 1024:.0f} MiB, "
+              f"{out['learn_rss'][mode]['samples']} samples, {out['learn_rss'][mode]['seconds']:.1f} s", flush=True)
+    assert out["learn_rss"]["dense"]["loss"] == out["learn_rss"]["compact"]["loss"]
+    return dict(compute=args.compute, reps=args.reps, warmup_rounds=3, unit="ms", **out)
+
+
 def learn(args):
     import spai_chess as sc
     cfg = dict(num_learn_iters=args.iters, num_self_play_iters=args.self_play_iters,
                num_parallel_self_play_games=args.games, batch_size=args.batch, num_epochs=args.epochs,
                num_searches=args.sims, blocks=args.blocks, seed=args.seed, clone_self_play=not args.distinct,
-               window=args.window, compute=args.compute)
+               window=args.window, compute=args.compute, samples=args.samples)
     with tempfile.TemporaryDirectory() as d:
         t0 = time.perf_counter()
         rec = sc.learn(checkpoint_dir=d, **cfg)
@@ -206,7 +314,13 @@ def main():
     ap.add_argument("--learn", action="store_true")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "chess_learner", "record.json"))
     ap.add_argument("--refresh-out", default=os.path.join(REPO, "profiles", "chess_refresh", "record.json"))
-    ap.add_argument("--sections", default="step,refresh", help="--bench: step, refresh or both, comma separated")
+    ap.add_argument("--sections", default="step,refresh",
+                    help="--bench: step, refresh, samples or several, comma separated")
+    ap.add_argument("--samples-out", default=os.path.join(REPO, "profiles", "chess_samples", "record.json"))
+    ap.add_argument("--train-samples", type=int, default=2048, help="--bench samples: samples of the timed train()")
+    ap.add_argument("--samples", choices=("dense", "compact"), default="dense",
+                    help="--learn: how the samples reach the learner")
+    ap.add_argument("--rss-child", choices=("dense", "compact"), default=None, help=argparse.SUPPRESS)
     ap.add_argument("--reps", type=int, default=20, help="--bench refresh: timed refreshes per route (at least 20)")
     ap.add_argument("--refresh-warmup", type=int, default=2)
     ap.add_argument("--commit", default=None, help="commit hash to record (default: git rev-parse HEAD)")
@@ -229,12 +343,14 @@ def main():
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
+    if args.rss_child:
+        return rss_child(args.rss_child)
     if not (args.bench or args.learn):
         ap.error("give --bench and/or --learn")
     sections = set(args.sections.split(","))
-    if not sections or sections - {"step", "refresh"}:
-        ap.error("--sections: step, refresh or both")
-    if args.bench and "refresh" in sections and args.reps < 20:
+    if not sections or sections - {"step", "refresh", "samples"}:
+        ap.error("--sections: step, refresh, samples")
+    if args.bench and sections & {"refresh", "samples"} and args.reps < 20:
         ap.error("--reps must be at least 20")
     commit = args.commit
     if commit is None:
@@ -253,6 +369,12 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.refresh_out)), exist_ok=True)
         with open(args.refresh_out, "w") as f:
             json.dump(dict(commit=commit, bench=refresh_bench(args)), f, indent=1)
+            f.write("\n")
+    if args.bench and "samples" in sections:
+        os.makedirs(os.path.dirname(os.path.abspath(args.samples_out)), exist_ok=True)
+        rec = dict(commit=commit, bench=samples_bench(args))
+        with open(args.samples_out, "w") as f:
+            json.dump(rec, f, indent=1)
             f.write("\n")
     if args.bench and "step" in sections:
         record["bench" + sfx] = bench(args)

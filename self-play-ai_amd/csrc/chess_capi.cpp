@@ -335,6 +335,12 @@ int spai_chess_selfplay_stream(spai_chess *e, uint32_t n_games, uint32_t window,
     return selfplay_run(e, n_games, game_id_base, sink, user, stats, window);
 }
 
+int spai_chess_selfplay_compact(spai_chess *e, uint32_t n_games, uint32_t window, uint64_t game_id_base,
+                                spai_chess_compact_sink sink, void *user, spai_selfplay_stats *stats) {
+    CH_CHECK(e);
+    return selfplay_run(e, n_games, game_id_base, nullptr, user, stats, window, sink);
+}
+
 int spai_chess_tree_children(spai_chess *e, uint32_t tree, uint16_t *moves, uint32_t *visits, uint32_t *n) {
     CH_CHECK(e);
     return tree_children(e, tree, moves, visits, n);

@@ -182,8 +182,22 @@ int tree_child_stats(spai_chess *e, uint32_t tree, uint16_t *moves, uint32_t *vi
                      uint32_t *n);
 int trees_advance(spai_chess *e, uint32_t n, const uint32_t *tree_idx, const uint32_t *child_index, uint8_t *status,
                   uint32_t *reps);
+// csink (with sink NULL): finished games go out as compact samples instead of dense arrays
 int selfplay_run(spai_chess *e, uint32_t n_games, uint64_t gid_base, spai_chess_sample_sink sink, void *user,
-                 spai_selfplay_stats *stats, uint32_t window = 0);
+                 spai_selfplay_stats *stats, uint32_t window = 0, spai_chess_compact_sink csink = nullptr);
+// visit-count policy of a root (mcts.rs:318-328): pol [4672] = set_prob(move, N), normalize
+void dense_policy(int side, uint32_t nch, const uint32_t *vis, const uint16_t *mv, float *pol);
+
+// chess_samples.hip: compact samples (spai_chess_sample).  samples_validate is the host check of
+// spai.h's rules, to run before any of the others reads a child array
+int samples_validate(uint32_t n, const spai_chess_sample *samples, const uint16_t *child_moves,
+                     const uint32_t *child_visits, uint32_t n_children_total);
+// the dense form by encode_host and dense_policy; any output may be NULL
+void samples_expand_host(uint32_t n, const spai_chess_sample *samples, const uint16_t *child_moves,
+                         const uint32_t *child_visits, float *states, float *policies, float *values);
+// the same dense form of B samples on the device, into batch_in [x: B*1216 | pi: B*4672 | z: B]
+int samples_expand_device(const spai_chess_sample *d_samples, const uint32_t *d_visits, const uint16_t *d_moves,
+                          uint32_t n_children_total, uint32_t B, float *batch_in, hipStream_t st);
 // chess_match.hip
 int match_run(spai_chess *e, const spai_chess_match_player *a, const spai_chess_match_player *b, uint32_t n_games,
               uint64_t gid_base, const spai_chess_match_config *cfg, spai_chess_match_game *games, uint16_t *moves,

@@ -78,6 +78,10 @@
 // In bf16 an MFMA chain runs over the whole K in one fp32 accumulator (the operand
 // rounding, 2^-9 relative, is far above the chain's own noise); the order is fixed.
 //
+// A step may also take its batch as compact self-play samples (spai_chess_sample):
+// the records are uploaded instead of the dense arrays and chess_samples.hip's
+// k_samples_expand writes batch_in from them, bit for bit the dense upload.
+//
 // This file holds what is chess's: the conv, weight-gradient and head kernels, the
 // step's launch chain and the entry points.  The BatchNorm and Adam kernels
 // (k_lc_bn_fwd<64>, k_lc_bn_bwd<64>, k_lc_adam), the workgroup reductions, the
@@ -694,6 +698,10 @@ struct Learner : lc::Core {   // batch_in: [x: B*1216 | pi: B*4672 | z: B]
     int capture = 0;
     uint32_t captured_batch = 0;           // the last step's batch if it was captured
     std::vector<DevBuf<float>> cap;        // per trunk conv: dz; then the masked gradient of the first policy conv
+    // compact samples (chess_samples.hip): a batch's records and their children [visits | moves]
+    uint32_t compact_batch = 0;            // the batch size the two buffers hold
+    DevBuf<spai_chess_sample> csamples;
+    DevBuf<uint32_t> cchildren;
 };
 
 }  // namespace chess
@@ -732,6 +740,18 @@ int alloc_batch(spai_chess_learner *L, uint32_t B) {
 int alloc_capture(spai_chess_learner *L) {
     for (auto &d : L->cap)
         if (!d.p) SPAI_TRY(d.alloc((size_t)L->max_batch * kHid * kCells));
+    return SPAI_OK;
+}
+
+// the device buffers of a compact batch of B samples: every sample may bring kMaxMoves children
+constexpr size_t kChildWords = (size_t)kMaxMoves * (4 + 2) / 4;   // uint32 visits + uint16 moves, in 4-byte words
+int alloc_compact(spai_chess_learner *L, uint32_t B) {
+    if (B <= L->compact_batch) return SPAI_OK;
+    SPAI_HIP(hipStreamSynchronize(L->stream));   // nothing in flight reads the old buffers
+    L->compact_batch = 0;
+    SPAI_TRY(L->csamples.alloc(B));
+    SPAI_TRY(L->cchildren.alloc((size_t)B * kChildWords));
+    L->compact_batch = B;
     return SPAI_OK;
 }
 
@@ -895,7 +915,49 @@ int train_batch(spai_chess_learner *L, uint32_t B, const float *states, const fl
     return SPAI_OK;
 }
 
+// one train step on B validated compact samples, sample i of the batch being
+// samples[index ? index[i] : i]: the records and the children they own go through the
+// pinned staging (which holds a dense batch, so it holds them) in one copy each, with
+// `first` rebuilt for the packed children; k_samples_expand writes batch_in; the step
+// itself is the dense one's
+int train_batch_compact(spai_chess_learner *L, uint32_t B, const spai_chess_sample *samples, const uint32_t *index,
+                        const uint16_t *child_moves, const uint32_t *child_visits, float *loss3) {
+    SPAI_CHECK(B >= 1 && B <= (1u << 16), SPAI_ERR_INVALID, "train_batch: batch of %u samples", B);
+    SPAI_TRY(alloc_batch(L, B));
+    SPAI_TRY(alloc_compact(L, B));
+    if (L->capture) SPAI_TRY(alloc_capture(L));
+    if (L->compute == SPAI_DTYPE_BF16) SPAI_TRY(alloc_shadow(L));
+    spai_chess_sample *hs = reinterpret_cast<spai_chess_sample *>(L->stage);
+    uint32_t total = 0;
+    for (uint32_t i = 0; i < B; ++i) {
+        hs[i] = samples[index ? index[i] : i];
+        total += hs[i].n_children;
+    }
+    uint32_t *hv = reinterpret_cast<uint32_t *>(hs + B);
+    uint16_t *hm = reinterpret_cast<uint16_t *>(hv + total);
+    uint32_t at = 0;
+    for (uint32_t i = 0; i < B; ++i) {
+        const uint32_t f = hs[i].first, k = hs[i].n_children;
+        memcpy(hv + at, child_visits + f, (size_t)k * 4);
+        memcpy(hm + at, child_moves + f, (size_t)k * 2);
+        hs[i].first = at;
+        at += k;
+    }
+    hipStream_t st = L->stream;
+    const uint32_t *dv = L->cchildren.p;
+    const uint16_t *dm = reinterpret_cast<const uint16_t *>(dv + total);
+    SPAI_HIP(hipMemcpyAsync(L->csamples.p, hs, (size_t)B * sizeof(spai_chess_sample), hipMemcpyHostToDevice, st));
+    SPAI_HIP(hipMemcpyAsync(L->cchildren.p, hv, (size_t)total * 6, hipMemcpyHostToDevice, st));
+    SPAI_TRY(samples_expand_device(L->csamples.p, dv, dm, total, B, L->batch_in.p, st));
+    bool finite = true;
+    SPAI_TRY(lc::run_step(*L, B, loss3, &finite, [&](int b) { return enqueue_step(L, b); }));
+    SPAI_CHECK(finite, SPAI_ERR_NAN, "chess learner: non-finite loss at step %llu", (unsigned long long)L->step);
+    return SPAI_OK;
+}
+
 void learner_free(spai_chess_learner *L) {
+    L->csamples.release();
+    L->cchildren.release();
     for (auto &d : L->z) d.release();
     for (auto &d : L->a) d.release();
     for (auto &d : L->cap) d.release();
@@ -1006,6 +1068,64 @@ int spai_chess_learner_train(spai_chess_learner *L, uint32_t n, const float *sta
                             [&](uint32_t m, const float *s, const float *p, const float *v) {
                                 return train_batch(L, m, s, p, v, loss);
                             });
+}
+
+int spai_chess_learner_train_batch_compact(spai_chess_learner *L, uint32_t n, const spai_chess_sample *samples,
+                                           const uint16_t *child_moves, const uint32_t *child_visits,
+                                           uint32_t n_children_total, float *loss) {
+    SPAI_PTR(L);
+    SPAI_PTR(samples);
+    SPAI_PTR(child_moves);
+    SPAI_PTR(child_visits);
+    SPAI_CHECK(n >= 1 && n <= (1u << 16), SPAI_ERR_INVALID, "train_batch: batch of %u samples", n);
+    SPAI_TRY(samples_validate(n, samples, child_moves, child_visits, n_children_total));
+    SPAI_SET_DEVICE(L);
+    return train_batch_compact(L, n, samples, nullptr, child_moves, child_visits, loss);
+}
+
+// Model::train over the n * repeat virtual samples: lc::train_epochs' loop with the
+// gather replaced by a list of sample indices
+int spai_chess_learner_train_compact(spai_chess_learner *L, uint32_t n, const spai_chess_sample *samples,
+                                     const uint16_t *child_moves, const uint32_t *child_visits,
+                                     uint32_t n_children_total, uint32_t repeat, uint32_t epochs, uint32_t batch,
+                                     uint64_t seed, float *loss) {
+    SPAI_PTR(L);
+    SPAI_PTR(samples);
+    SPAI_PTR(child_moves);
+    SPAI_PTR(child_visits);
+    SPAI_CHECK(n >= 1 && batch >= 1, SPAI_ERR_INVALID, "train: need samples and a batch size");
+    SPAI_CHECK(repeat >= 1 && (uint64_t)n * repeat <= 0xFFFFFFFFull, SPAI_ERR_INVALID,
+               "train: repeat %u of %u samples (need repeat >= 1 and n * repeat < 2^32)", repeat, n);
+    SPAI_TRY(samples_validate(n, samples, child_moves, child_visits, n_children_total));
+    SPAI_SET_DEVICE(L);
+    const uint32_t nv = n * repeat;
+    SPAI_TRY(lc::adam_reset(*L, L->stream));
+    std::vector<uint32_t> perm;
+    choose_multiple(nv, nv, seed, 0x7EA1Bull, perm);
+    batch = std::min(batch, nv);
+    std::vector<uint32_t> index(batch);
+    const uint32_t nb = (nv + batch - 1) / batch;
+    for (uint32_t ep = 0; ep < epochs; ++ep)
+        for (uint32_t b = 0; b < nb; ++b) {
+            const uint32_t lo = b * batch, m = std::min(batch, nv - lo);
+            for (uint32_t i = 0; i < m; ++i) index[i] = perm[lo + i] % n;
+            SPAI_TRY(train_batch_compact(L, m, samples, index.data(), child_moves, child_visits, loss));
+        }
+    return SPAI_OK;
+}
+
+int spai_chess_learner_batch(spai_chess_learner *L, float *states, float *policies, float *values, uint32_t n) {
+    SPAI_PTR(L);
+    SPAI_CHECK(L->last_batch > 0, SPAI_ERR_INVALID, "no train step yet");
+    SPAI_CHECK(n == L->last_batch, SPAI_ERR_INVALID, "the last step's batch has %u samples, not %u", L->last_batch, n);
+    SPAI_SET_DEVICE(L);
+    const float *x = L->batch_in.p, *pi = x + (size_t)n * kEnc, *z = pi + (size_t)n * kPolicy;
+    hipStream_t st = L->stream;
+    if (states) SPAI_HIP(hipMemcpyAsync(states, x, (size_t)n * kEnc * 4, hipMemcpyDeviceToHost, st));
+    if (policies) SPAI_HIP(hipMemcpyAsync(policies, pi, (size_t)n * kPolicy * 4, hipMemcpyDeviceToHost, st));
+    if (values) SPAI_HIP(hipMemcpyAsync(values, z, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    SPAI_HIP(hipStreamSynchronize(st));
+    return SPAI_OK;
 }
 
 int spai_chess_learner_params(spai_chess_learner *L, float *params, size_t n_params) {

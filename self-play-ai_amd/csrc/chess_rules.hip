@@ -78,29 +78,7 @@ __global__ void k_slots_apply(Board *__restrict__ boards, uint64_t *__restrict__
     }
 }
 
-// get_encoding (chess.rs:176-249): lane = (row, col) cell of the side to move's view
-__device__ __forceinline__ void encode_cell(const Board &b, uint32_t reps, int lane, float v[kPlanes]) {
-    const int me = b.side;
-    const int row = lane >> 3, col = lane & 7;
-    const int rank = me == WHITE ? row : 7 - row;
-    const int sq = rank * 8 + col;
-    const bb mine = me == WHITE ? b.col[WHITE] : b.col[BLACK];
-    const bb theirs = me == WHITE ? b.col[BLACK] : b.col[WHITE];
-#pragma unroll
-    for (int p = 0; p < 6; ++p) {
-        v[p] = ((b.pc[p] & mine) >> sq) & 1 ? 1.0f : 0.0f;
-        v[6 + p] = ((b.pc[p] & theirs) >> sq) & 1 ? 1.0f : 0.0f;
-    }
-    const int ck = me == WHITE ? 1 : 4, cq = me == WHITE ? 2 : 8, tk = me == WHITE ? 4 : 1, tq = me == WHITE ? 8 : 2;
-    v[12] = (b.castle & ck) ? 1.0f : 0.0f;
-    v[13] = (b.castle & cq) ? 1.0f : 0.0f;
-    v[14] = (b.castle & tk) ? 1.0f : 0.0f;
-    v[15] = (b.castle & tq) ? 1.0f : 0.0f;
-    v[16] = (float)reps;
-    v[17] = (float)b.fifty / 100.0f;
-    v[18] = (float)(b.made / 2) / 50.0f;
-}
-
+// get_encoding: encode_cell (chess.h), one wave per slot
 __global__ void k_slots_encode(const Board *__restrict__ boards, const uint64_t *__restrict__ hist,
                                const uint32_t *__restrict__ n_hist, uint32_t max_hist, uint32_t first, uint32_t n,
                                float *out) {

@@ -712,6 +712,8 @@ int root_stats(spai_chess *e, uint32_t na) {
     return SPAI_OK;
 }
 
+}  // namespace
+
 // visit-count policy of a root (mcts.rs:318-328): set_prob(action, N), normalize
 void dense_policy(int side, uint32_t nch, const uint32_t *vis, const uint16_t *mv, float *pol) {
     std::fill(pol, pol + kPolicy, 0.0f);
@@ -720,7 +722,6 @@ void dense_policy(int side, uint32_t nch, const uint32_t *vis, const uint16_t *m
     for (uint32_t k = 0; k < nch; ++k) pol[policy_index(side, mv[k])] = (float)vis[k];
     for (int i = 0; i < kPolicy; ++i) pol[i] = pol[i] / tot;
 }
-}  // namespace
 
 int search(spai_chess *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, float *policy,
            uint32_t *child_ids, float *child_visits, uint16_t *child_moves, uint32_t *n_children, double *evals) {
@@ -868,8 +869,10 @@ int tree_root(spai_chess *e, uint32_t tree, spai_chess_state *root, uint32_t *vi
 // whose game ended taking the next game (a fresh start-position tree) before the
 // next search; each game's draws are keyed by its id and its own move number, so
 // every game is the one the lockstep run plays.
+// csink (with sink NULL, spai_chess_selfplay_compact): only the emit branch differs, a
+// finished game's records go out as they are, with no encode_host and no dense_policy.
 int selfplay_run(spai_chess *e, uint32_t n_games, uint64_t gid_base, spai_chess_sample_sink sink, void *user,
-                 spai_selfplay_stats *stats, uint32_t window) {
+                 spai_selfplay_stats *stats, uint32_t window, spai_chess_compact_sink csink) {
     const auto t0 = std::chrono::steady_clock::now();
     const uint32_t W = (window == 0 || window >= n_games) ? n_games : window;   // tree slots
     SPAI_CHECK(n_games >= 1 && W <= e->cfg.max_trees, SPAI_ERR_INVALID, "%u tree slots (max_trees %u)", W,
@@ -901,6 +904,8 @@ int selfplay_run(spai_chess *e, uint32_t n_games, uint64_t gid_base, spai_chess_
     std::vector<Board> nb;
     std::vector<float> enc, pol, val;
     std::vector<uint16_t> mvs;
+    std::vector<spai_chess_sample> cs;
+    std::vector<uint32_t> cvis;
     // optional per-move trace (diagnostics): SPAI_TRACE_MOVES=<csv path>, lines of
     // move, active games, leaves evaluated, seconds (search + root statistics)
     std::unique_ptr<FILE, int (*)(FILE *)> trace(nullptr, &std::fclose);
@@ -978,6 +983,23 @@ int selfplay_run(spai_chess *e, uint32_t n_games, uint64_t gid_base, spai_chess_
                 }
                 sink(user, (uint32_t)(gid_base + slot_game[t]), (uint32_t)m, enc.data(), pol.data(), val.data(),
                      mvs.data());
+            } else if (csink) {
+                cs.resize(m);
+                mvs.clear();
+                cvis.clear();
+                for (size_t h = 0; h < m; ++h) {
+                    spai_chess_sample &r = cs[h];
+                    r.state = to_abi(H[h].board, H[h].reps);
+                    r.value = H[h].board.side == cur ? v : -v;
+                    r.move = H[h].move;
+                    r.n_children = (uint16_t)H[h].mv.size();
+                    r.first = (uint32_t)mvs.size();
+                    r.pad = 0;
+                    mvs.insert(mvs.end(), H[h].mv.begin(), H[h].mv.end());
+                    cvis.insert(cvis.end(), H[h].vis.begin(), H[h].vis.end());
+                }
+                csink(user, (uint32_t)(gid_base + slot_game[t]), (uint32_t)m, cs.data(), mvs.data(), cvis.data(),
+                      (uint32_t)mvs.size());
             }
             hist[t].clear();
             hist[t].shrink_to_fit();

@@ -188,17 +188,13 @@ inline int core_grow_batch(Core &c, uint32_t B) {
     return SPAI_OK;
 }
 
-// one train step on B <= max_batch samples: stage and upload the batch, the game's
-// enqueue_step(B), the loss terms back, one synchronisation, the loss sums.
-// finite (may be NULL): whether the loss sums are finite.
+// what follows a batch's way into batch_in, whatever brought it there (the upload
+// below, or work already enqueued on the stream: the chess learner's compact
+// samples): the game's enqueue_step(B), the loss terms back, one synchronisation,
+// the loss sums.  finite (may be NULL): whether the loss sums are finite.
 template <class Enqueue>
-int train_batch(Core &c, uint32_t B, const float *states, const float *policies, const float *values, float *loss3,
-                bool *finite, Enqueue &&enqueue_step) {
+int run_step(Core &c, uint32_t B, float *loss3, bool *finite, Enqueue &&enqueue_step) {
     hipStream_t st = c.stream;
-    memcpy(c.stage, states, (size_t)B * c.xw * 4);
-    memcpy(c.stage + (size_t)B * c.xw, policies, (size_t)B * c.pw * 4);
-    memcpy(c.stage + (size_t)B * (c.xw + c.pw), values, (size_t)B * 4);
-    SPAI_HIP(hipMemcpyAsync(c.batch_in.p, c.stage, (size_t)B * c.row() * 4, hipMemcpyHostToDevice, st));
     SPAI_TRY(enqueue_step((int)B));
     float *terms = c.stage + (size_t)B * c.row();
     SPAI_HIP(hipMemcpyAsync(terms, c.terms.p, (size_t)B * 2 * 4, hipMemcpyDeviceToHost, st));
@@ -206,6 +202,17 @@ int train_batch(Core &c, uint32_t B, const float *states, const float *policies,
     const bool ok = sum_loss(terms, B, loss3);
     if (finite) *finite = ok;
     return SPAI_OK;
+}
+
+// one train step on B <= max_batch samples: stage and upload the batch, then run_step
+template <class Enqueue>
+int train_batch(Core &c, uint32_t B, const float *states, const float *policies, const float *values, float *loss3,
+                bool *finite, Enqueue &&enqueue_step) {
+    memcpy(c.stage, states, (size_t)B * c.xw * 4);
+    memcpy(c.stage + (size_t)B * c.xw, policies, (size_t)B * c.pw * 4);
+    memcpy(c.stage + (size_t)B * (c.xw + c.pw), values, (size_t)B * 4);
+    SPAI_HIP(hipMemcpyAsync(c.batch_in.p, c.stage, (size_t)B * c.row() * 4, hipMemcpyHostToDevice, c.stream));
+    return run_step(c, B, loss3, finite, enqueue_step);
 }
 
 // the parameters or the gradients to the host

@@ -62,6 +62,8 @@ SYMBOLS = [
     "spai_chess_match_config_default", "spai_chess_match_run", "spai_chess_tree_children",
     "spai_chess_tree_child_stats",
     "spai_chess_match_set_one_stream",
+    "spai_chess_selfplay_compact", "spai_chess_samples_expand", "spai_chess_learner_train_batch_compact",
+    "spai_chess_learner_train_compact", "spai_chess_learner_batch",
     # tictactoe (spai_ttt.py)
     "spai_ttt_create", "spai_ttt_destroy", "spai_ttt_games_resize", "spai_ttt_games_write", "spai_ttt_games_read",
     "spai_ttt_legal_mask", "spai_ttt_apply", "spai_ttt_encode", "spai_ttt_mask_invalid", "spai_ttt_net_num_params",

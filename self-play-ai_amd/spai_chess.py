@@ -8,6 +8,7 @@ Mirrors the reference's chess surface (joshua16266261/self-play-ai):
   SelfPlayWorker::self_play        -> ChessEngine.self_play
   play() (main.rs:54-135)          -> ChessEngine.match
   Model::train (model/mod.rs)      -> ChessLearner.train_batch / train
+  (compact self-play samples)      -> ChessSamples, self_play(samples="compact"), learn(samples="compact")
   Learner::learn (learner.rs)      -> learn
 Every call goes through the HIP library; there is no CPU fallback.
 """
@@ -28,6 +29,13 @@ assert STATE_DTYPE.itemsize == 80
 
 SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                    C.POINTER(C.c_float), C.POINTER(C.c_uint16))
+
+# spai_chess_sample and its sink
+SAMPLE_DTYPE = np.dtype([("state", STATE_DTYPE), ("value", "<f4"), ("move", "<u2"), ("n_children", "<u2"),
+                         ("first", "<u4"), ("pad", "<u4")])
+assert SAMPLE_DTYPE.itemsize == 96
+COMPACT_SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint16),
+                           C.POINTER(C.c_uint32), C.c_uint32)
 
 
 class ChessMatchPlayer(C.Structure):
@@ -114,6 +122,11 @@ def lib():
         L.spai_chess_learner_set_capture.argtypes = [vp, i32]
         L.spai_chess_learner_gradient.argtypes = [vp, i32, vp, C.c_size_t]
         L.spai_chess_learner_logits.argtypes = [vp, vp, C.c_size_t]
+        L.spai_chess_selfplay_compact.argtypes = [vp, u32, u32, u64, COMPACT_SINK, vp, P(SelfPlayStats)]
+        L.spai_chess_samples_expand.argtypes = [u32, vp, vp, vp, u32, vp, vp, vp]
+        L.spai_chess_learner_train_batch_compact.argtypes = [vp, u32, vp, vp, vp, u32, vp]
+        L.spai_chess_learner_train_compact.argtypes = [vp, u32, vp, vp, vp, u32, u32, u32, u32, u64, vp]
+        L.spai_chess_learner_batch.argtypes = [vp, vp, vp, vp, u32]
         _ready = True
     return L
 
@@ -165,6 +178,97 @@ def states_from(boards):
         a[i]["fifty"] = b.get("fifty", 0)
         a[i]["made"] = b.get("made", 0)
     return a
+
+
+class ChessSamples:
+    """Compact self-play samples (spai_chess_sample): per sample the searched position,
+    the value and the move played (`samples`, SAMPLE_DTYPE), and the root children of
+    all of them CSR-style, child_moves (uint16 move codes, MoveGen order) and
+    child_visits (uint32 N), sample i owning [first, first + n_children) of both.
+    `game` holds each sample's game id.  About 100 bytes plus 6 per legal move instead
+    of the 23,556 of the dense form, which expand() builds on the host and
+    ChessLearner.train_batch / train build on the device.
+
+    repeat: the set stands for its samples repeated that many times (virtual sample
+    j is sample j % n), as learn's clone_self_play repeats a batch of games; len(),
+    game and expand() are those of the repeated set, the arrays are stored once."""
+
+    def __init__(self, samples, child_moves, child_visits, game=None, repeat=1):
+        self.samples = np.ascontiguousarray(samples, SAMPLE_DTYPE).reshape(-1)
+        self.child_moves = np.ascontiguousarray(child_moves, np.uint16).reshape(-1)
+        self.child_visits = np.ascontiguousarray(child_visits, np.uint32).reshape(-1)
+        if len(self.child_moves) != len(self.child_visits):
+            raise ValueError("child_moves and child_visits differ in length")
+        self._game = (np.zeros(len(self.samples), np.int64) if game is None
+                      else np.ascontiguousarray(game, np.int64).reshape(-1))
+        if len(self._game) != len(self.samples):
+            raise ValueError("one game id per sample")
+        if int(repeat) < 1:
+            raise ValueError("repeat must be >= 1")
+        self.repeat = int(repeat)
+
+    @property
+    def n(self):
+        """stored samples (len() counts the repeats)"""
+        return len(self.samples)
+
+    def __len__(self):
+        return self.n * self.repeat
+
+    @property
+    def game(self):
+        return np.tile(self._game, self.repeat)
+
+    @property
+    def nbytes(self):
+        """bytes of the stored sample records and children"""
+        return self.samples.nbytes + self.child_moves.nbytes + self.child_visits.nbytes
+
+    def with_repeat(self, repeat):
+        """the same arrays (not copied) standing for `repeat` repetitions"""
+        return ChessSamples(self.samples, self.child_moves, self.child_visits, self._game, repeat)
+
+    @staticmethod
+    def concat(parts):
+        """one set of the parts' stored samples in ascending game id (a stable sort: a
+        game's samples keep their move order), children packed in that order and `first`
+        rebuilt; repeat 1"""
+        parts = list(parts)
+        if not parts:
+            return ChessSamples(np.zeros(0, SAMPLE_DTYPE), [], [])
+        smp = np.concatenate([q.samples for q in parts])
+        game = np.concatenate([q._game for q in parts])
+        base = np.cumsum([0] + [len(q.child_moves) for q in parts[:-1]])
+        first = np.concatenate([q.samples["first"].astype(np.int64) + b for q, b in zip(parts, base)])
+        smp["first"] = first
+        whole = ChessSamples(smp, np.concatenate([q.child_moves for q in parts]),
+                             np.concatenate([q.child_visits for q in parts]), game)
+        return whole.take(np.argsort(game, kind="stable"))
+
+    def take(self, idx):
+        """the stored samples idx, in that order, as a set of their own: their children
+        packed in that order and `first` rebuilt; repeat 1"""
+        idx = np.asarray(idx, np.int64).reshape(-1)
+        smp = self.samples[idx].copy()
+        nch = smp["n_children"].astype(np.int64)
+        new_first = np.cumsum(nch) - nch
+        # entry k of sample i moves from first[i] + k to new_first[i] + k
+        src = np.repeat(smp["first"].astype(np.int64) - new_first, nch) + np.arange(int(nch.sum()))
+        smp["first"] = new_first
+        return ChessSamples(smp, self.child_moves[src], self.child_visits[src], self._game[idx])
+
+    def expand(self):
+        """the dense form (enc [len][1216], policy [len][4672], value [len]) through
+        spai_chess_samples_expand: what self-play's dense sink hands over, bit for bit"""
+        n = self.n
+        enc = np.zeros((n, ENC), np.float32)
+        pol = np.zeros((n, POLICY), np.float32)
+        val = np.zeros(n, np.float32)
+        _check(lib().spai_chess_samples_expand(n, _p(self.samples), _p(self.child_moves), _p(self.child_visits),
+                                               len(self.child_moves), _p(enc), _p(pol), _p(val)))
+        if self.repeat > 1:
+            enc, pol, val = np.tile(enc, (self.repeat, 1)), np.tile(pol, (self.repeat, 1)), np.tile(val, self.repeat)
+        return enc, pol, val
 
 
 class ChessEngine:
@@ -363,10 +467,28 @@ class ChessEngine:
         """measurement only: both chains of later matches on the engine's stream (default: two streams)"""
         _check(lib().spai_chess_match_set_one_stream(self.h, 1 if on else 0))
 
-    def self_play(self, n_games, game_id_base=0, keep=True, keep_policy=True, window=None):
+    def self_play(self, n_games, game_id_base=0, keep=True, keep_policy=True, window=None, samples="dense"):
         """SelfPlayWorker::self_play over n_games games; window: play them through
-        that many tree slots (spai_chess_selfplay_stream), games in finishing order"""
+        that many tree slots (spai_chess_selfplay_stream), games in finishing order.
+        samples="compact" (spai_chess_selfplay_compact): the same games, each game's
+        dict holding game, n and samples, a ChessSamples, instead of the dense enc /
+        policy / value / moves arrays (which its expand() and samples["move"] give back)"""
+        if samples not in ("dense", "compact"):
+            raise ValueError(f'samples must be "dense" or "compact", got {samples!r}')
         games = []
+        if samples == "compact":
+            def csink(user, gid, n, smp, mv, vis, total):
+                if keep:
+                    a = np.frombuffer(C.string_at(smp, n * SAMPLE_DTYPE.itemsize), SAMPLE_DTYPE).copy()
+                    games.append(dict(game=gid, n=n, samples=ChessSamples(
+                        a, np.ctypeslib.as_array(mv, (total,)).copy(), np.ctypeslib.as_array(vis, (total,)).copy(),
+                        np.full(n, gid, np.int64))))
+
+            ccb = COMPACT_SINK(csink)
+            st = SelfPlayStats()
+            _check(lib().spai_chess_selfplay_compact(self.h, n_games, 0 if window is None else int(window),
+                                                     game_id_base, ccb, None, C.byref(st)))
+            return games, {k: getattr(st, k) for k, _ in SelfPlayStats._fields_}
 
         def sink(user, gid, n, enc, pol, val, moves):
             if keep:
@@ -476,6 +598,45 @@ class ChessLearner(DeviceLearner):
         if compute != "f32":
             self.set_compute(compute)
 
+    def train_batch(self, states, policies=None, values=None):
+        """one train step on dense arrays, or on a ChessSamples (given alone), whose dense
+        form a HIP kernel writes on the device from the uploaded records: the same bits"""
+        if not isinstance(states, ChessSamples):
+            return super().train_batch(states, policies, values)
+        cs = states
+        if policies is not None or values is not None:
+            raise ValueError("a ChessSamples is given alone")
+        if cs.repeat != 1:
+            raise ValueError("train_batch takes the samples as they are (repeat 1); train() repeats them")
+        loss = np.zeros(3, np.float32)
+        self._call("train_batch_compact", self.h, cs.n, _p(cs.samples), _p(cs.child_moves), _p(cs.child_visits),
+                   len(cs.child_moves), _p(loss))
+        return loss
+
+    def train(self, states, policies=None, values=None, epochs=1, batch=32, seed=0):
+        """Model::train on dense arrays, or on a ChessSamples (given alone): over its
+        len() = n * repeat virtual samples, bit-identical to train(*samples.expand()),
+        with neither the dense arrays nor the repeats ever built on the host"""
+        if not isinstance(states, ChessSamples):
+            return super().train(states, policies, values, epochs=epochs, batch=batch, seed=seed)
+        cs = states
+        if policies is not None or values is not None:
+            raise ValueError("a ChessSamples is given alone")
+        loss = np.zeros(3, np.float32)
+        self._call("train_compact", self.h, cs.n, _p(cs.samples), _p(cs.child_moves), _p(cs.child_visits),
+                   len(cs.child_moves), cs.repeat, epochs, batch, seed, _p(loss))
+        return loss
+
+    def batch(self):
+        """the last train step's batch as the step read it on the device, whichever route
+        brought it there: (enc [B][1216], policy [B][4672], value [B])"""
+        B = self.last_batch()
+        enc = np.zeros((B, ENC), np.float32)
+        pol = np.zeros((B, POLICY), np.float32)
+        val = np.zeros(B, np.float32)
+        self._call("batch", self.h, _p(enc), _p(pol), _p(val), B)
+        return enc, pol, val
+
     def set_compute(self, compute):
         """between steps: parameters, Adam moments and step count are kept"""
         if compute not in self.COMPUTE:
@@ -520,7 +681,7 @@ class ChessLearner(DeviceLearner):
 def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_games=100, batch_size=32, num_epochs=4,
           num_searches=600, temperature=1.25, c=2.0, blocks=10, seed=0, checkpoint_dir=".", clone_self_play=True,
           params=None, device=0, on_train_set=None, window=None, max_moves=None, compute="f32", refresh="device",
-          on_phase=None):
+          on_phase=None, samples="dense"):
     """Learner::learn (learner.rs:98-196) for chess, with mcts.rs:46-59's defaults:
     per iteration i, self-play with the current weights on one ChessEngine (the net
     refreshed in place), Model::train on the samples, checkpoint i.safetensors.
@@ -538,6 +699,11 @@ def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_ga
     device parameters; "host": ChessNet.set_params(learner.params()), the same kernels
     behind a host round trip.  Both give the same bits.  on_phase(i, name, seconds)
     receives the host time of each phase (learn_loop).
+    samples: "dense" (the default), or "compact": self-play hands over ChessSamples
+    and the learner expands them on the device, so the loop never builds a dense
+    array; clone_self_play then trains with repeat=num_self_play_iters instead of
+    tiling, and on_train_set(i, samples, None, None, game_ids) receives the
+    ChessSamples.  Both give the same checkpoints, byte for byte.
     Returns per-iteration records: samples, loss [total, policy, value] of the last
     step, games, checkpoint."""
     G = num_parallel_self_play_games
@@ -545,6 +711,15 @@ def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_ga
         raise ValueError(f"compute {compute!r}: 'f32' or 'bf16'")
     if refresh not in ("device", "host"):
         raise ValueError(f'refresh must be "device" or "host", got {refresh!r}')
+    if samples not in ("dense", "compact"):
+        raise ValueError(f'samples must be "dense" or "compact", got {samples!r}')
+    hooks = {}
+    if samples == "compact":
+        def join(parts, repeat):
+            cs = ChessSamples.concat(parts).with_repeat(repeat)
+            return (cs,), (cs, None, None, cs.game)
+
+        hooks = dict(gather=lambda games: ChessSamples.concat(g["samples"] for g in games), join=join)
     return learn_loop(
         lambda: ChessEngine(num_searches=num_searches, max_trees=G if window is None else int(window),
                             eval_kind=EVAL_NET, device=device, c=c, temperature=temperature, seed=seed,
@@ -552,5 +727,5 @@ def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_ga
         lambda eng, P: ChessNet(eng, blocks, P), lambda eng, P: ChessLearner(eng, blocks, P, compute=compute),
         init_params(blocks, seed) if params is None else params, blocks, 256, GAME_CHESS, num_learn_iters,
         num_self_play_iters, G, batch_size, num_epochs, seed, checkpoint_dir, clone_self_play, on_train_set,
-        self_play_kw=dict(window=window),
-        refresh=(lambda net, L: net.set_params(L)) if refresh == "device" else None, on_phase=on_phase)
+        self_play_kw=dict(window=window, samples=samples),
+        refresh=(lambda net, L: net.set_params(L)) if refresh == "device" else None, on_phase=on_phase, **hooks)

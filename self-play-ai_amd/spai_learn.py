@@ -92,6 +92,18 @@ def _samples(games):
             np.concatenate([g["value"] for g in games]))
 
 
+def _gather(games):
+    """learn_loop's default gather: one self-play batch -> (states, policies, values, game ids)"""
+    games = sorted(games, key=lambda g: g["game"])
+    return _samples(games) + (np.concatenate([np.full(len(g["value"]), g["game"], np.int64) for g in games]),)
+
+
+def _join(parts, repeat):
+    """learn_loop's default join: the batches' dense arrays concatenated, `repeat` times over"""
+    s, p, v, g = (np.concatenate([q[k] for q in parts * repeat]) for k in range(4))
+    return (s, p, v), (s, p, v, g)
+
+
 def _iter_seed(seed, i):
     """the training permutation's seed of learn iteration i"""
     return (int(seed) * 0x9E3779B97F4A7C15 + i + 1) & 0xFFFFFFFFFFFFFFFF
@@ -99,7 +111,8 @@ def _iter_seed(seed, i):
 
 def learn_loop(make_engine, make_net, make_learner, params, blocks, hidden, game, num_learn_iters,
                num_self_play_iters, num_parallel_self_play_games, batch_size, num_epochs, seed, checkpoint_dir,
-               clone_self_play, on_train_set, self_play_kw=None, refresh=None, on_phase=None):
+               clone_self_play, on_train_set, self_play_kw=None, refresh=None, on_phase=None, gather=_gather,
+               join=_join):
     """Learner::learn (learner.rs:98-196), the body of spai_ttt.learn, spai_chess.learn and
     spai.learn (their docstrings say what it does): make_engine() -> the self-play engine,
     make_net(eng, P) and make_learner(eng, P) on it, self_play_kw the keyword
@@ -107,7 +120,13 @@ def learn_loop(make_engine, make_net, make_learner, params, blocks, hidden, game
     refresh(net, L) brings the learner's weights into the self-play net before every
     iteration but the first (default: net.set_params(L.params())); on_phase(i, name,
     seconds) receives the host time of iteration i's "refresh", of each of its "self_play"
-    batches and of its "train"."""
+    batches and of its "train".
+    How the samples travel: gather(games) -> one self-play batch's part, and
+    join(parts, repeat) -> (the arguments of L.train, the arguments of on_train_set
+    after i), repeat being num_self_play_iters under clone_self_play and 1 otherwise;
+    the last on_train_set argument holds one game id per training sample.  The
+    defaults are dense arrays, concatenated and tiled (spai_chess.learn's compact
+    samples replace both)."""
     if refresh is None:
         def refresh(net, L):
             net.set_params(L.params())
@@ -130,27 +149,23 @@ def learn_loop(make_engine, make_net, make_learner, params, blocks, hidden, game
                 refresh(net, L)
                 phase(i, "refresh", t0)
             batches = 1 if clone_self_play else num_self_play_iters
-            parts, gids, n_games = [], [], 0
+            parts, n_games = [], 0
             for b in range(batches):
                 base = (i * num_self_play_iters + b) * G
                 t0 = time.perf_counter()
                 games, _ = eng.self_play(G, game_id_base=base, **(self_play_kw or {}))
                 phase(i, "self_play", t0)
                 n_games += len(games)
-                parts.append(_samples(games))
-                gids.append(np.concatenate([np.full(len(g["value"]), g["game"], np.int64)
-                                            for g in sorted(games, key=lambda g: g["game"])]))
-            if clone_self_play:
-                parts, gids = parts * num_self_play_iters, gids * num_self_play_iters
-            s, p, v = (np.concatenate([q[k] for q in parts]) for k in range(3))
+                parts.append(gather(games))
+            train_args, seen = join(parts, num_self_play_iters if clone_self_play else 1)
             if on_train_set is not None:
-                on_train_set(i, s, p, v, np.concatenate(gids))
+                on_train_set(i, *seen)
             t0 = time.perf_counter()
-            loss = L.train(s, p, v, epochs=num_epochs, batch=batch_size, seed=_iter_seed(seed, i))
+            loss = L.train(*train_args, epochs=num_epochs, batch=batch_size, seed=_iter_seed(seed, i))
             phase(i, "train", t0)
             path = os.path.join(checkpoint_dir, f"{i}.safetensors")
             spai.save_params(path, L.params(), blocks, hidden, game=game)   # spai_params_save_safetensors
-            out.append(dict(iteration=i, samples=int(len(v)), loss=[float(x) for x in loss], games=n_games,
+            out.append(dict(iteration=i, samples=int(len(seen[-1])), loss=[float(x) for x in loss], games=n_games,
                             checkpoint=path))
     finally:
         L.close()
