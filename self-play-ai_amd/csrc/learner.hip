@@ -31,12 +31,9 @@
 namespace spai {
 namespace {
 
-constexpr int kCells = 42, kRows = 6, kCols = 7;
-constexpr int kPad = 72;          // (6+2) x (7+2) zero-padded plane
-constexpr int kPlane = 73;        // its LDS stride (odd, so channels spread over the banks)
+constexpr int kCells = 42, kCols = 7;
+constexpr int kPlane = 73;        // LDS stride of a (6+2) x (7+2) zero-padded plane (odd, so channels spread over the banks)
 constexpr int kThreads = 256;
-constexpr int kTickDbias = 8;     // BatchNorm hand-off counters: tick[0..7] channel slices, tick[8] the bias-gradient merge
-constexpr int kTicks = 16;
 
 // ------------------------------------------------------------------ conv 3x3 on f32 MFMA
 // Every conv of the step is a GEMM on v_mfma_f32_16x16x4_f32 (exact f32: an
@@ -57,59 +54,8 @@ __host__ __device__ inline int round16(int c) { return (c + 15) & ~15; }
 // tap offset inside a zero-padded 8 x 9 plane
 __device__ __forceinline__ int tap_off(int tap) { return (tap / 3 - 1) * 9 + (tap % 3 - 1); }
 
-// stage a sample's input planes [c][kPlane], zero-padded (rows -1..6, cols -1..7), channels >= cin zero.
-// All of a thread's loads are issued before its LDS stores, so the staging pays
-// one memory round trip, not one per element.
-constexpr int kStageMax = (64 * kPad + kThreads - 1) / kThreads;   // 18 elements per thread at 64 channels
-__device__ __forceinline__ void load_planes(const float *__restrict__ xb, int cin, int cinp, float (&v)[kStageMax]) {
-    const int n = cinp * kPad;
-#pragma unroll
-    for (int j = 0; j < kStageMax; ++j) {
-        const int i = threadIdx.x + j * kThreads;
-        const int c = i / kPad, r = i - c * kPad, h = r / 9 - 1, x = r % 9 - 1;
-        v[j] = (i < n && c < cin && h >= 0 && h < kRows && x >= 0 && x < kCols) ? xb[c * kCells + h * kCols + x] : 0.f;
-    }
-}
-__device__ __forceinline__ void store_planes(const float (&v)[kStageMax], int cinp, float *xs) {
-    const int n = cinp * kPad;
-#pragma unroll
-    for (int j = 0; j < kStageMax; ++j) {
-        const int i = threadIdx.x + j * kThreads;
-        if (i < n) xs[(i / kPad) * kPlane + i % kPad] = v[j];
-    }
-}
-constexpr int kDzMax = (64 * 44 + kThreads - 1) / kThreads;
-__device__ __forceinline__ void load_dz(const float *__restrict__ dzb, int cout, int coutp, float (&v)[kDzMax]) {
-#pragma unroll
-    for (int j = 0; j < kDzMax; ++j) {
-        const int i = threadIdx.x + j * kThreads, n = i / 44, p = i - n * 44;
-        v[j] = (i < coutp * 44 && n < cout && p < kCells) ? dzb[n * kCells + p] : 0.f;
-    }
-}
-__device__ __forceinline__ void store_dz(const float (&v)[kDzMax], int coutp, float *ds) {
-#pragma unroll
-    for (int j = 0; j < kDzMax; ++j) {
-        const int i = threadIdx.x + j * kThreads;
-        if (i < coutp * 44) ds[i] = v[j];
-    }
-}
-__device__ __forceinline__ void stage_planes(const float *__restrict__ xb, int cin, int cinp, float *xs) {
-    float v[kStageMax];
-    const int n = cinp * kPad;
-#pragma unroll
-    for (int j = 0; j < kStageMax; ++j) {
-        const int i = threadIdx.x + j * kThreads;
-        const int c = i / kPad, r = i - c * kPad, h = r / 9 - 1, x = r % 9 - 1;
-        v[j] = (i < n && c < cin && h >= 0 && h < kRows && x >= 0 && x < kCols) ? xb[c * kCells + h * kCols + x] : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < kStageMax; ++j) {
-        const int i = threadIdx.x + j * kThreads;
-        if (i < n) xs[(i / kPad) * kPlane + i % kPad] = v[j];
-    }
-}
-
-// stage_planes without per-element index math: thread t < 252 owns cell t % 42
+// stage a sample's input planes [c][kPlane], zero-padded (rows -1..6, cols -1..7),
+// channels >= cin zero, without per-element index math: thread t < 252 owns cell t % 42
 // of channels t / 42 + 6j (source and LDS offsets are the thread's base plus
 // immediates), thread t < 240 zeroes border cell t % 30 of channels t / 30 + 8j;
 // the two sets are disjoint, so one barrier after the call covers both.
@@ -143,10 +89,7 @@ __device__ __forceinline__ void stage_planes_fast(const float *__restrict__ xb, 
 // step (blockIdx.y = entry of the table built at learner_create):
 //   desc[8 y ..] = {param offset, cin, cout, cinp, coutp, dgrad, packed offset, 0}
 constexpr int kPackDesc = 8;
-// (it also zeroes the BatchNorm hand-off counters ahead of the step's convs)
-__global__ void k_pack_all(const float *__restrict__ P, const uint32_t *__restrict__ desc, float *__restrict__ wall,
-                           unsigned *__restrict__ tick) {
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < kTicks) tick[threadIdx.x] = 0u;
+__global__ void k_pack_all(const float *__restrict__ P, const uint32_t *__restrict__ desc, float *__restrict__ wall) {
     const uint32_t *d = desc + kPackDesc * blockIdx.y;
     const int cin = (int)d[1], cout = (int)d[2], cinp = (int)d[3], coutp = (int)d[4];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -159,255 +102,17 @@ __global__ void k_pack_all(const float *__restrict__ P, const uint32_t *__restri
     wall[d[6] + i] = v;
 }
 
-// BatchNorm (train mode) of a conv's input, applied while the consumer conv
-// stages it (MODE & kBnIn).  The producer conv (MODE & kStatsOut) leaves
-// per-(channel, sample) partials {sum, centred sum of squares} over the 42 cells,
-// and the last of its workgroups to finish a channel slice merges that slice's B
-// partials in a fixed order (Chan's pairwise variance: N var = sum_b Q_b + 42
-// sum_b (m_b - mean)^2) into the batch mean / invstd and the running statistics
-// (momentum, unbiased variance) -- what k_bn_fwd did in a kernel of its own.  The
-// consumer stages a = relu(gamma (z - mean) invstd + beta [+ res]) from those
-// 4 x 64 floats; its slice-0 workgroups write a (the backward's mask and
-// weight-gradient input).
-//
-// The hand-off inside the producer launch (cdna_hip_programming.md §6 Guideline
-// 16, counter form): every partial is stored write-through (sc1), each storing
-// wave drains, the workgroup barrier, then one lane's agent-scope ticket add; the
-// workgroup that draws the slice's last ticket reads the partials with sc1 loads
-// and resets the counter.  The merge order is fixed, so the result does not
-// depend on which workgroup finishes last.
-constexpr int kBnIn = 1, kStatsOut = 2, kBnGrad = 4, kGradStats = 8;
-typedef __attribute__((address_space(1))) unsigned long long gu64;
-typedef __attribute__((address_space(1))) unsigned int gu32;
-struct BnIn {
-    float2 *part;                 // [c][B] producer partials (kStatsOut)
-    const float *gamma, *beta;
-    const float *res;             // residual (block input) [B][cin][42], or null
-    float *a_out;                 // activations [B][cin][42]
-    float *mean, *invstd, *run_mean, *run_var;
-    int B;
-    float eps, momentum;
-    unsigned *tick;               // the producer's slice counters
-};
-constexpr int kBnStatFloats = 5 * 64;   // LDS: per input channel 4 (forward) or 5 (backward) statistics
-constexpr int kLdsFlags = 4;            // LDS: the ticket results
-
-__device__ __forceinline__ void store_part(float2 *p, float x, float y) {   // write-through (sc1)
-    const unsigned long long u = ((unsigned long long)__float_as_uint(y) << 32) | __float_as_uint(x);
-    __hip_atomic_store((gu64 *)p, u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float2 load_part(const float2 *p) {   // sc1: no stale L1 copy
-    const unsigned long long u = __hip_atomic_load((gu64 *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return make_float2(__uint_as_float((unsigned)u), __uint_as_float((unsigned)(u >> 32)));
-}
-__device__ __forceinline__ void store_part1(float *p, float x) {
-    __hip_atomic_store((gu32 *)p, __float_as_uint(x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float load_part1(const float *p) {
-    return __uint_as_float(__hip_atomic_load((gu32 *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-// sum over the tpc consecutive lanes of a channel (butterfly: the same value on each)
-__device__ __forceinline__ float chan_sum(float v, int tpc) {
-    for (int o = 1; o < tpc; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// the merge of channels [c0, c0 + ch) of a forward producer (ch = 16 or 64: 16 or
-// 4 lanes per channel, samples strided over them)
-__device__ __forceinline__ void fin_bn_fwd(const BnIn &bo, int c0, int ch, int cout) {
-    const int tpc = kThreads / ch, c = c0 + threadIdx.x / tpc, q = threadIdx.x % tpc, B = bo.B;
-    const bool ok = c < cout;
-    const float2 *pp = bo.part + (size_t)c * B;
-    float s = 0.f;
-    if (ok)
-        for (int b = q; b < B; b += tpc) s += load_part(pp + b).x;
-    s = chan_sum(s, tpc);
-    const int n = B * kCells;
-    const float mu = s / (float)n;
-    float q2 = 0.f;
-    if (ok)
-        for (int b = q; b < B; b += tpc) {
-            const float2 v = load_part(pp + b);
-            const float d = v.x / (float)kCells - mu;
-            q2 += v.y + (float)kCells * (d * d);
-        }
-    q2 = chan_sum(q2, tpc);
-    if (q == 0 && ok) {
-        const float var = q2 / (float)n;
-        bo.mean[c] = mu;
-        bo.invstd[c] = 1.0f / sqrtf(var + bo.eps);
-        bo.run_mean[c] = (1.0f - bo.momentum) * bo.run_mean[c] + bo.momentum * mu;
-        bo.run_var[c] = (1.0f - bo.momentum) * bo.run_var[c] +
-                        bo.momentum * (n > 1 ? var * (float)n / (float)(n - 1) : var);
-    }
-}
-
-// The backward of a = relu(bn(z) [+ res]) fused the same way (kBnGrad): the
-// producer of da (the data gradient of the layer above, kGradStats) leaves per
-// (channel, sample) partials {sum dy, sum dy xhat} with dy = da [a > 0] and
-// xhat = (z - mean) invstd, and its slice's last workgroup merges them into
-// dbeta = sum dy and dgamma = sum dy xhat; the consumer (this layer's
-// data-gradient conv) stages dz = gamma invstd / N (N dy - dbeta - xhat dgamma)
-// (k_bn_bwd's arithmetic), writing dz for the weight gradient and dy for the
-// residual's skip path from its slice-0 workgroups.  Those also leave per-sample
-// sums of dz, merged by their last workgroup into the conv bias gradient.
-struct BnGrad {
-    const float *a, *z, *mean, *invstd, *gamma;
-    const float *dgamma, *dbeta;  // merged by the producer of da
-    float *dz_out, *dy_out;       // [B][c][42] (dy_out may be null)
-    float *db_part, *dbias;       // [c][B] per-sample dz sums; the conv bias gradient
-    unsigned *tick;
-    int B;
-};
-struct GradStats {                // the partials for the layer whose da this conv produces
-    const float *a, *z, *mean, *invstd;
-    float2 *part;                 // [c][B]
-    float *dgamma, *dbeta;        // that layer's merged gradients
-    unsigned *tick;
-};
-
-__device__ __forceinline__ void fin_bn_grad(const GradStats &gs, int c0, int ch, int cout, int B) {
-    const int tpc = kThreads / ch, c = c0 + threadIdx.x / tpc, q = threadIdx.x % tpc;
-    const bool ok = c < cout;
-    const float2 *pp = gs.part + (size_t)c * B;
-    float s1 = 0.f, s2 = 0.f;
-    if (ok)
-        for (int b = q; b < B; b += tpc) {
-            const float2 v = load_part(pp + b);
-            s1 += v.x;
-            s2 += v.y;
-        }
-    s1 = chan_sum(s1, tpc);
-    s2 = chan_sum(s2, tpc);
-    if (q == 0 && ok) {
-        gs.dbeta[c] = s1;
-        gs.dgamma[c] = s2;
-    }
-}
-
-__device__ __forceinline__ void bn_grad_stats(const BnGrad &bg, int cin, float *st) {
-    const int c = threadIdx.x;
-    if (c < cin) {
-        const float is = bg.invstd[c];
-        st[c] = bg.dbeta[c];
-        st[64 + c] = bg.dgamma[c];
-        st[128 + c] = bg.mean[c];
-        st[192 + c] = is;
-        st[256 + c] = bg.gamma[c] * is / (float)(bg.B * kCells);
-    }
-}
-
-// stage dz of this layer (k_bn_bwd's arithmetic) from da, a, z; slice 0 writes dz and dy
-template <int CINP>
-__device__ __forceinline__ void stage_planes_dz(const float *__restrict__ dab, int cin, const BnGrad &bg, size_t boff,
-                                                const float *st, float *xs) {
-    const int t = threadIdx.x;
-    if (t < 252) {
-        const int c0 = t / kCells, cell = t - c0 * kCells;
-        float *dst = xs + c0 * kPlane + (cell / kCols + 1) * 9 + cell % kCols + 1;
-        constexpr int J = (CINP + 5) / 6;
-        float vd[J], va[J], vz[J];
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            const bool ok = c0 + 6 * j < cin;
-            vd[j] = ok ? dab[t + 252 * j] : 0.f;
-            va[j] = ok ? bg.a[boff + t + 252 * j] : 0.f;
-            vz[j] = ok ? bg.z[boff + t + 252 * j] : 0.f;
-        }
-        const bool w = blockIdx.y == 0;
-        const float n = (float)(bg.B * kCells);
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            const int c = c0 + 6 * j;
-            if (c < CINP) {
-                float v = 0.f;
-                if (c < cin) {
-                    const float d = va[j] > 0.f ? vd[j] : 0.f;
-                    const float x = (vz[j] - st[128 + c]) * st[192 + c];
-                    v = st[256 + c] * (n * d - st[c] - x * st[64 + c]);
-                    if (w) {
-                        bg.dz_out[boff + t + 252 * j] = v;
-                        if (bg.dy_out) bg.dy_out[boff + t + 252 * j] = d;
-                    }
-                }
-                dst[6 * kPlane * j] = v;
-            }
-        }
-    }
-    if (t < 240) {
-        const int c0 = t / 30, bi = t - c0 * 30;
-        const int k = bi - 18;
-        const int off = bi < 9 ? bi : bi < 18 ? 63 + bi - 9 : 9 * (1 + k / 2) + ((k & 1) ? 8 : 0);
-        float *dst = xs + c0 * kPlane + off;
-#pragma unroll
-        for (int j = 0; j < (CINP + 7) / 8; ++j)
-            if (c0 + 8 * j < CINP) dst[8 * kPlane * j] = 0.f;
-    }
-}
-
-// per-channel statistics of the input (merged by its producer) -> LDS st[4][64]
-__device__ __forceinline__ void bn_in_stats(const BnIn &bn, int cin, float *st) {
-    const int c = threadIdx.x;
-    if (c < cin) {
-        st[c] = bn.mean[c];
-        st[64 + c] = bn.invstd[c];
-        st[128 + c] = bn.gamma[c];
-        st[192 + c] = bn.beta[c];
-    }
-}
-
-// stage_planes_fast of relu(bn(z) [+ res]) (k_bn_fwd's arithmetic); a written by the slice-0 workgroups
-template <int CINP>
-__device__ __forceinline__ void stage_planes_bn(const float *__restrict__ zb, int cin, const BnIn &bn, size_t boff,
-                                                const float *st, float *xs) {
-    const int t = threadIdx.x;
-    if (t < 252) {
-        const int c0 = t / kCells, cell = t - c0 * kCells;
-        float *dst = xs + c0 * kPlane + (cell / kCols + 1) * 9 + cell % kCols + 1;
-        float v[(CINP + 5) / 6], r[(CINP + 5) / 6];
-#pragma unroll
-        for (int j = 0; j < (CINP + 5) / 6; ++j) {
-            v[j] = c0 + 6 * j < cin ? zb[t + 252 * j] : 0.f;
-            r[j] = bn.res && c0 + 6 * j < cin ? bn.res[boff + t + 252 * j] : 0.f;
-        }
-        const bool wa = bn.a_out && blockIdx.y == 0;
-#pragma unroll
-        for (int j = 0; j < (CINP + 5) / 6; ++j) {
-            const int c = c0 + 6 * j;
-            if (c < CINP) {
-                float a = 0.f;
-                if (c < cin) {
-                    float y = st[128 + c] * ((v[j] - st[c]) * st[64 + c]) + st[192 + c];
-                    if (bn.res) y += r[j];
-                    a = fmaxf(y, 0.f);
-                    if (wa) bn.a_out[boff + t + 252 * j] = a;
-                }
-                dst[6 * kPlane * j] = a;
-            }
-        }
-    }
-    if (t < 240) {
-        const int c0 = t / 30, bi = t - c0 * 30;
-        const int k = bi - 18;
-        const int off = bi < 9 ? bi : bi < 18 ? 63 + bi - 9 : 9 * (1 + k / 2) + ((k & 1) ? 8 : 0);
-        float *dst = xs + c0 * kPlane + off;
-#pragma unroll
-        for (int j = 0; j < (CINP + 7) / 8; ++j)
-            if (c0 + 8 * j < CINP) dst[8 * kPlane * j] = 0.f;
-    }
-}
-
 // workgroup (sample, slice): 3 position tiles (48 rows, 42 real) x NT channel
 // tiles of output channels [16 NT slice, 16 NT (slice + 1)); wave w owns channel
 // tile w % NT and K part w / NT (KS = 4/NT parts, summed in LDS in a fixed
 // order).  CINP (input channels padded to 4) and NT are compile-time, so the
 // k-loop unrolls fully and the weight loads of a whole part are in flight
 // together.  coutp_all = the packed matrix's row length (all output channels).
-template <int CINP, int NT, int MODE = 0, int MTS = 3>
+template <int CINP, int NT>
 __global__ __launch_bounds__(kThreads) void k_conv_mfma(const float *__restrict__ in, int cin,
                                                         const float *__restrict__ wk, const float *__restrict__ bias,
                                                         int cout, int coutp_all, float *__restrict__ out,
-                                                        int accumulate, BnIn bn, BnIn bo, BnGrad bg, GradStats gs) {
+                                                        int accumulate) {
     constexpr int KS = 4 / NT, CSN = CINP / 4, KSTEPS = 9 * CSN, PER = KSTEPS / KS;
     static_assert(4 % NT == 0 && KSTEPS % KS == 0, "4 waves: NT channel tiles x KS whole K parts");
     extern __shared__ float sm[];
@@ -418,43 +123,28 @@ __global__ __launch_bounds__(kThreads) void k_conv_mfma(const float *__restrict_
     const int s0 = part * PER;
     const int row = lane & 15, kq = lane >> 4;
     // this wave's weights first: their loads are in flight while the planes stage
-    const int co0 = MTS == 3 ? 16 * NT * (int)blockIdx.y : 0;
+    const int co0 = 16 * NT * (int)blockIdx.y;
     const float *wl = wk + (size_t)(4 * s0 + kq) * coutp_all + co0 + nt * 16 + row;
     float bq[PER];
 #pragma unroll
     for (int i = 0; i < PER; ++i) bq[i] = wl[(size_t)i * 4 * coutp_all];
-    if constexpr ((MODE & kBnIn) != 0) {
-        float *st = sm + CINP * kPlane + 2 * 2304;
-        bn_in_stats(bn, cin, st);
-        __syncthreads();
-        stage_planes_bn<CINP>(in + (size_t)b * cin * kCells, cin, bn, (size_t)b * cin * kCells, st, xs);
-    } else if constexpr ((MODE & kBnGrad) != 0) {
-        float *st = sm + CINP * kPlane + 2 * 2304;
-        bn_grad_stats(bg, cin, st);
-        __syncthreads();
-        stage_planes_dz<CINP>(in + (size_t)b * cin * kCells, cin, bg, (size_t)b * cin * kCells, st, xs);
-    } else {
-        stage_planes_fast<CINP>(in + (size_t)b * cin * kCells, cin, xs);
-    }
+    stage_planes_fast<CINP>(in + (size_t)b * cin * kCells, cin, xs);
     __syncthreads();
-    // MTS = 3: the workgroup covers all 3 position tiles and blockIdx.y picks the
-    // channel slice; MTS = 1: blockIdx.y picks the position tile (all channels)
-    const int mt0 = MTS == 3 ? 0 : (int)blockIdx.y;
     // per-lane A base of each position tile, biased by the most negative tap
     // offset (-10) so every k-step's offset is a non-negative immediate.  Rows past
     // the 42 cells read cell 0: D row i depends only on A row i, and those rows are
     // never stored, so the k-loop has no select (a per-MFMA exec branch kept the
     // scheduler from running LDS reads ahead: one exposed LDS round trip per MFMA)
-    const float *xb[MTS];
+    const float *xb[3];
 #pragma unroll
-    for (int mt = 0; mt < MTS; ++mt) {
-        const int p = (mt0 + mt) * 16 + row;
+    for (int mt = 0; mt < 3; ++mt) {
+        const int p = mt * 16 + row;
         const int pp = p < kCells ? p : 0;
         xb[mt] = xs + kq * kPlane + (pp / kCols + 1) * 9 + pp % kCols + 1 - 10;
     }
-    f32x4 acc[MTS];
+    f32x4 acc[3];
 #pragma unroll
-    for (int mt = 0; mt < MTS; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int mt = 0; mt < 3; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
     // the wave's K part as a compile-time constant: every LDS offset is an immediate
     auto kloop = [&](auto part_c) {
         constexpr int s0c = decltype(part_c)::value * PER;
@@ -463,7 +153,7 @@ __global__ __launch_bounds__(kThreads) void k_conv_mfma(const float *__restrict_
             const int s = s0c + i, tap = s / CSN, cs = s % CSN;
             const int off = 4 * cs * kPlane + tap_off(tap) + 10;
 #pragma unroll
-            for (int mt = 0; mt < MTS; ++mt)
+            for (int mt = 0; mt < 3; ++mt)
                 acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[mt][off], bq[i], acc[mt], 0, 0, 0);
         }
     };
@@ -482,7 +172,7 @@ __global__ __launch_bounds__(kThreads) void k_conv_mfma(const float *__restrict_
         if (part > 0) {
             float *dst = red + (((part - 1) * 3) * 64 + lane) * 4 + nt * (3 * 3 * 64 * 4);
 #pragma unroll
-            for (int mt = 0; mt < MTS; ++mt)
+            for (int mt = 0; mt < 3; ++mt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) dst[mt * 64 * 4 + r] = acc[mt][r];
         }
@@ -492,133 +182,29 @@ __global__ __launch_bounds__(kThreads) void k_conv_mfma(const float *__restrict_
         for (int q = 1; q < KS; ++q) {
             const float *src = red + (((q - 1) * 3) * 64 + lane) * 4 + nt * (3 * 3 * 64 * 4);
 #pragma unroll
-            for (int mt = 0; mt < MTS; ++mt)
+            for (int mt = 0; mt < 3; ++mt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[mt][r] += src[mt * 64 * 4 + r];
         }
     }
     const int n = co0 + nt * 16 + row;   // D[row = 4 kq + r][col = lane & 15]: col = channel, row = position
-    // the waves that hold a finished tile (part 0); no early return: every wave
-    // reaches the hand-off's barriers below
+    // the waves that hold a finished tile (part 0).  A named flag: written into the `if`,
+    // the short-circuit becomes control flow and the K-split kernels compile to other
+    // code (the kernel's bytes are pinned, profiles/learner_bn_fuse_retirement)
     const bool live = (KS == 1 || part == 0) && n < cout;
-    const int b0 = (int)gridDim.x;   // the partials' row length: the batch
     if (live) {
         const float bv = bias ? bias[n] : 0.f;
         float *ob = out + ((size_t)b * cout + n) * kCells;
-        float fin[MTS][4];   // the stored values (kGradStats)
 #pragma unroll
-        for (int mt = 0; mt < MTS; ++mt)
+        for (int mt = 0; mt < 3; ++mt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int p = (mt0 + mt) * 16 + 4 * kq + r;
-                fin[mt][r] = 0.f;
+                const int p = mt * 16 + 4 * kq + r;
                 if (p < kCells) {
                     const float v = acc[mt][r] + bv;
-                    fin[mt][r] = accumulate ? ob[p] + v : v;
-                    ob[p] = fin[mt][r];
+                    ob[p] = accumulate ? ob[p] + v : v;
                 }
             }
-        if constexpr ((MODE & kGradStats) != 0) {   // the next BN backward's partials of channel n, sample b
-            static_assert(MTS == 3, "statistics need the whole board");
-            const size_t base = ((size_t)b * cout + n) * kCells;
-            const float mu = gs.mean[n], is = gs.invstd[n];
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int mt = 0; mt < MTS; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int p = (mt0 + mt) * 16 + 4 * kq + r;
-                    if (p < kCells) {
-                        const float d = gs.a[base + p] > 0.f ? fin[mt][r] : 0.f;
-                        s1 += d;
-                        s2 += d * ((gs.z[base + p] - mu) * is);
-                    }
-                }
-            s1 += __shfl_xor(s1, 16, 64);
-            s1 += __shfl_xor(s1, 32, 64);
-            s2 += __shfl_xor(s2, 16, 64);
-            s2 += __shfl_xor(s2, 32, 64);
-            if (kq == 0) store_part(gs.part + (size_t)n * b0 + b, s1, s2);
-        }
-        if constexpr ((MODE & kStatsOut) != 0) {   // the consumer's BN partials of channel n, sample b
-            static_assert(MTS == 3, "statistics need the whole board");
-            float s = 0.f;
-#pragma unroll
-            for (int mt = 0; mt < MTS; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if ((mt0 + mt) * 16 + 4 * kq + r < kCells) s += acc[mt][r] + bv;
-            s += __shfl_xor(s, 16, 64);   // the 4 lanes of the channel, a fixed order, the same value on each
-            s += __shfl_xor(s, 32, 64);
-            const float m = s / (float)kCells;
-            float q = 0.f;
-#pragma unroll
-            for (int mt = 0; mt < MTS; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if ((mt0 + mt) * 16 + 4 * kq + r < kCells) {
-                        const float d = (acc[mt][r] + bv) - m;
-                        q += d * d;
-                    }
-            q += __shfl_xor(q, 16, 64);
-            q += __shfl_xor(q, 32, 64);
-            if (kq == 0) store_part(bo.part + (size_t)n * b0 + b, s, q);
-        }
-    }
-    constexpr bool kStats = (MODE & (kStatsOut | kGradStats)) != 0, kDb = (MODE & kBnGrad) != 0;
-    if constexpr (kStats || kDb) {
-        static_assert(MTS == 3, "the hand-off counts whole-board workgroups");
-        // kBnGrad: the slice-0 workgroups' per-sample bias-gradient partials, sum_p dz
-        // over the staged planes (4 lanes per channel, a fixed order)
-        const bool dbw = kDb && blockIdx.y == 0;
-        if (dbw) {
-            const int c = threadIdx.x >> 2, q = threadIdx.x & 3;
-            float s = 0.f;
-            if (c < cin)
-                for (int p = q; p < kCells; p += 4) s += xs[c * kPlane + (p / kCols + 1) * 9 + p % kCols + 1];
-            s = chan_sum(s, 4);
-            if (q == 0 && c < cin) store_part1(bg.db_part + (size_t)c * b0 + b, s);
-        }
-        float *flag = sm + CINP * kPlane + 2 * 2304 + kBnStatFloats;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave drains its sc1 stores
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned *tick = kStats ? ((MODE & kStatsOut) ? bo.tick : gs.tick) : nullptr;
-            float l1 = 0.f, l2 = 0.f;
-            if (kStats) {
-                const unsigned t = __hip_atomic_fetch_add((gu32 *)(tick + blockIdx.y), 1u, __ATOMIC_RELAXED,
-                                                          __HIP_MEMORY_SCOPE_AGENT);
-                if (t == gridDim.x - 1) {
-                    l1 = 1.f;
-                    __hip_atomic_store((gu32 *)(tick + blockIdx.y), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-            if (dbw) {
-                const unsigned t = __hip_atomic_fetch_add((gu32 *)(bg.tick + kTickDbias), 1u, __ATOMIC_RELAXED,
-                                                          __HIP_MEMORY_SCOPE_AGENT);
-                if (t == gridDim.x - 1) {
-                    l2 = 1.f;
-                    __hip_atomic_store((gu32 *)(bg.tick + kTickDbias), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-            flag[0] = l1;
-            flag[1] = l2;
-        }
-        __syncthreads();
-        // the last arrival merges (sc1 loads: no acquire needed, Guideline 16)
-        if (kStats && flag[0] != 0.f) {
-            const int ch = 16 * NT, c0 = MTS == 3 ? 16 * NT * (int)blockIdx.y : 0;
-            if constexpr ((MODE & kStatsOut) != 0) fin_bn_fwd(bo, c0, ch, cout);
-            if constexpr ((MODE & kGradStats) != 0) fin_bn_grad(gs, c0, ch, cout, b0);
-        }
-        if (kDb && flag[1] != 0.f) {   // the conv bias gradient: 4 lanes per channel, a fixed order
-            const int c = threadIdx.x >> 2, q = threadIdx.x & 3;
-            float s = 0.f;
-            if (c < cin)
-                for (int bb = q; bb < b0; bb += 4) s += load_part1(bg.db_part + (size_t)c * b0 + bb);
-            s = chan_sum(s, 4);
-            if (q == 0 && c < cin) bg.dbias[c] = s;
-        }
     }
 }
 
@@ -630,19 +216,19 @@ __global__ __launch_bounds__(kThreads) void k_conv_mfma(const float *__restrict_
 // tiles), reduction = each sample's 42 positions (11 k-steps of 4).
 constexpr int kWgSamples = 4;
 constexpr int kWgMaxTiles = 3;   // tiles per wave (144 tiles / 12 groups / 4 waves at 64 x 64: 384 workgroups at B = 128)
-// BIAS: one more GEMM column k = K over a plane of ones, part[..][n][K] = sum_p dz:
-// the conv bias gradient (for the layers whose BN backward runs in the data
-// gradient's staging, kBnGrad)
-template <int CINP, bool BIAS>
+template <int CINP>
 __global__ __launch_bounds__(kThreads) void k_wgrad_mfma(const float *__restrict__ x, int cin,
                                                          const float *__restrict__ dz, int cout, int B, int groups,
                                                          float *__restrict__ part) {
-    constexpr int K = 9 * CINP, K1 = K + (BIAS ? 1 : 0), Kp = (K1 + 15) & ~15, NK = Kp / 16;
+    constexpr int K = 9 * CINP, Kp = (K + 15) & ~15, NK = Kp / 16;
     extern __shared__ float sm[];
     const int coutp = round16(cout), NTo = coutp / 16, ntiles = NTo * NK;
     float *xs = sm;                        // [CINP][kPlane]
     float *ds = sm + CINP * kPlane;        // [coutp][44], zero past 42 and past cout
-    float *ones = ds + coutp * 44;         // BIAS: [kPlane] of 1.0
+    // the end of the LDS in use, computed here: with coutp * 44 first evaluated in the
+    // zero fill below, the compiler orders the prologue's scalar code differently
+    // (the kernel's bytes are pinned, profiles/learner_bn_fuse_retirement)
+    const float *sm_end = ds + coutp * 44;
     const int chunk = blockIdx.x, group = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = lane & 15, kq = lane >> 4;
     // this wave's tiles: group's range [t0, t1), wave-strided
@@ -669,9 +255,7 @@ __global__ __launch_bounds__(kThreads) void k_wgrad_mfma(const float *__restrict
     constexpr int NX = (CINP * kCells + kThreads - 1) / kThreads;   // 11 at 64 channels
     constexpr int ND = (64 * kCells + kThreads - 1) / kThreads;     // cout <= 64
     const int nx = cin * kCells, nd = cout * kCells;
-    for (int i = threadIdx.x; i < CINP * kPlane + coutp * 44; i += kThreads) sm[i] = 0.f;
-    if (BIAS)
-        for (int i = threadIdx.x; i < kPlane; i += kThreads) ones[i] = 1.f;
+    for (int i = threadIdx.x; i < (int)(sm_end - sm); i += kThreads) sm[i] = 0.f;
     int dx[NX], dd[ND];
 #pragma unroll
     for (int j = 0; j < NX; ++j) {
@@ -709,8 +293,8 @@ __global__ __launch_bounds__(kThreads) void k_wgrad_mfma(const float *__restrict
             const int k = kt * 16 + row;                      // B[kk = position][n = k]
             const bool kval = k < K;
             const int tap = k / CINP, c = k % CINP;           // CINP: compile-time
-            // a padding column (k >= K1) reads position data too: its D column is never stored
-            const float *xcol = BIAS && k == K ? ones : xs + (kval ? c * kPlane + tap_off(tap) : 0);
+            // a padding column (k >= K) reads position data too: its D column is never stored
+            const float *xcol = xs + (kval ? c * kPlane + tap_off(tap) : 0);
 #pragma unroll
             for (int s = 0; s < 11; ++s) {
                 const float av = arow[4 * s + kq];
@@ -729,7 +313,7 @@ __global__ __launch_bounds__(kThreads) void k_wgrad_mfma(const float *__restrict
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int n = mt * 16 + 4 * kq + r;
-            if (n < cout && k < K1) part[((size_t)chunk * cout + n) * K1 + k] = acc[j][r];
+            if (n < cout && k < K) part[((size_t)chunk * cout + n) * K + k] = acc[j][r];
         }
     }
 }
@@ -738,13 +322,12 @@ __global__ __launch_bounds__(kThreads) void k_wgrad_mfma(const float *__restrict
 // batch 128 there are 32 chunks: all 32 loads in flight at once, and 64-thread
 // workgroups (576 of them for 64 x 64, instead of 144 of 256 threads on 256 CUs)
 constexpr int kWgReduceBatch = 32, kWgReduceThreads = 64;
-__global__ void k_wgrad_reduce(const float *__restrict__ part, int B, int cin, int cout, float *__restrict__ dw,
-                               float *__restrict__ dbias) {
+__global__ void k_wgrad_reduce(const float *__restrict__ part, int B, int cin, int cout, float *__restrict__ dw) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int cinp = round4(cin), K0 = 9 * cinp, K = K0 + (dbias ? 1 : 0);   // (the bias column k = K0)
+    const int cinp = round4(cin), K = 9 * cinp;
     if (i < cout * K) {   // i = n * K + k: consecutive threads read consecutive partials (coalesced)
         const int n = i / K, k = i - n * K, tap = k / cinp, c = k - tap * cinp;
-        if (c < cin || k == K0) {
+        if (c < cin) {
             const float *src = part + i;
             const size_t stride = (size_t)cout * K;
             float s = 0.f;
@@ -756,8 +339,7 @@ __global__ void k_wgrad_reduce(const float *__restrict__ part, int B, int cin, i
                 for (int j = 0; j < kWgReduceBatch; ++j)
                     if (b0 + j < B) s += v[j];
             }
-            if (k == K0) dbias[n] = s;
-            else dw[((size_t)n * cin + c) * 9 + tap] = s;
+            dw[((size_t)n * cin + c) * 9 + tap] = s;
         }
     }
 }
@@ -900,41 +482,24 @@ __global__ __launch_bounds__(kBn) void k_bn_bwd(const float *__restrict__ da, co
 // one workgroup per sample: policy logits (1344 -> 7), value (126 -> 1, tanh),
 // loss terms and the output gradients
 //   dlogits = (softmax * sum(pi) - pi) / B,  dpre = 2 (v - z) / B * (1 - v^2)
-// FUSED: rp / rv are the head convs' z, and their BatchNorm + ReLU (train mode,
-// k_bn_fwd's arithmetic) is applied here from the convs' partials (BnIn), writing
-// the activations a for the backward
-template <bool FUSED>
 __global__ __launch_bounds__(kThreads) void k_heads_loss(const float *__restrict__ rp, const float *__restrict__ rv,
                                                          const float *__restrict__ wp, const float *__restrict__ bp,
                                                          const float *__restrict__ wv, const float *__restrict__ bv,
                                                          const float *__restrict__ pi, const float *__restrict__ zv,
                                                          int B, float *__restrict__ dlogits, float *__restrict__ dpre,
-                                                         float *__restrict__ loss_terms, BnIn bnp, BnIn bnv) {
+                                                         float *__restrict__ loss_terms) {
     __shared__ float part[kThreads / 64][8];
-    __shared__ float stp[FUSED ? kBnStatFloats : 1], stv[FUSED ? kBnStatFloats : 1];
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float *xp = rp + (size_t)b * 32 * kCells, *xv = rv + (size_t)b * 3 * kCells;
-    if constexpr (FUSED) {
-        bn_in_stats(bnp, 32, stp);
-        bn_in_stats(bnv, 3, stv);
-        __syncthreads();
-    }
-    auto act = [&](float z, const float *st, int c, float *a_out, int k) {
-        if constexpr (!FUSED) return z;
-        const float y = fmaxf(st[128 + c] * ((z - st[c]) * st[64 + c]) + st[192 + c], 0.f);
-        a_out[k] = y;
-        return y;
-    };
     // one pass over the features: 7 policy logits and the value pre-activation at
     // once; wave sums by shuffles, then the 4 wave partials in order
     float acc8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int k = threadIdx.x; k < 32 * kCells; k += kThreads) {
-        const float xk = act(xp[k], stp, k / kCells, bnp.a_out + (size_t)b * 32 * kCells, k);
+        const float xk = xp[k];
 #pragma unroll
         for (int o = 0; o < 7; ++o) acc8[o] += xk * wp[o * 32 * kCells + k];
     }
-    for (int k = threadIdx.x; k < 3 * kCells; k += kThreads)
-        acc8[7] += act(xv[k], stv, k / kCells, bnv.a_out + (size_t)b * 3 * kCells, k) * wv[k];
+    for (int k = threadIdx.x; k < 3 * kCells; k += kThreads) acc8[7] += xv[k] * wv[k];
 #pragma unroll
     for (int o = 0; o < 8; ++o) {
 #pragma unroll
@@ -1084,16 +649,12 @@ int learner_alloc_batch(spai_learner *L, uint32_t B) {
     }
     SPAI_TRY(L->d0.alloc(act));
     SPAI_TRY(L->d1.alloc(act));
-    // trunk + the two heads' partials, the bias-gradient partials [64][B], the hand-off counters
-    SPAI_TRY(L->bn_part.alloc((size_t)(2 * L->blocks + 3) * L->hidden * B * 2 + (size_t)L->hidden * B + kTicks));
-    SPAI_TRY(L->d2.alloc(act));
-    if (L->blocks > 0) SPAI_TRY(L->dzb.alloc((size_t)2 * L->blocks * B * L->hidden * kCells));
     SPAI_TRY(L->dlogits.alloc((size_t)B * 7));
     SPAI_TRY(L->dpre.alloc(B));
     SPAI_TRY(L->loss_terms.alloc((size_t)B * 2));
     const size_t cmax = (size_t)std::max(L->hidden, 32);
     for (auto &w : L->wpart_side)   // weight-gradient partials per chunk (one buffer per side stream)
-        SPAI_TRY(w.alloc((size_t)((B + kWgSamples - 1) / kWgSamples) * cmax * (9 * round4(L->hidden) + 1)));
+        SPAI_TRY(w.alloc((size_t)((B + kWgSamples - 1) / kWgSamples) * cmax * 9 * round4(L->hidden)));
     L->max_batch = B;
     return SPAI_OK;
 }
@@ -1110,84 +671,50 @@ int learner_alloc_batch(spai_learner *L, uint32_t B) {
 // leave one workgroup per CU, whose staging, k-loop and K-part sum then run back to
 // back instead of overlapping another workgroup's; profiles/r05/learner/spw.)
 
-template <int CINP, int MODE>
-int launch_conv_t(int B, size_t lds, hipStream_t st, const float *in, int cin, const float *wk, const float *bias,
-                  int cout, float *out, int acc, const BnIn &bn, const BnIn &bo, const BnGrad &bg, const GradStats &gs) {
+template <int CINP>
+int launch_conv_t(int B, hipStream_t st, const float *in, int cin, const float *wk, const float *bias, int cout,
+                  float *out, int acc) {
     constexpr int ks = 9 * CINP / 4;
+    const size_t lds = ((size_t)CINP * kPlane + 2 * 2304) * sizeof(float);
     const int nt = round16(cout) / 16;
     if constexpr (ks % 4 == 0) {
-        k_conv_mfma<CINP, 1, MODE><<<dim3(B, nt), kThreads, lds, st>>>(in, cin, wk, bias, cout, 16 * nt, out, acc, bn,
-                                                                      bo, bg, gs);
+        k_conv_mfma<CINP, 1><<<dim3(B, nt), kThreads, lds, st>>>(in, cin, wk, bias, cout, 16 * nt, out, acc);
         return SPAI_OK;
-    }
-    if (nt == 4) {
-        k_conv_mfma<CINP, 4, MODE><<<dim3(B), kThreads, lds, st>>>(in, cin, wk, bias, cout, 64, out, acc, bn, bo,
-                                                                  bg, gs);
-        return SPAI_OK;
-    }
-    set_error("learner conv: %d input / %d output channels not built", cin, cout);
-    return SPAI_ERR_UNSUPPORTED;
-}
-
-// bn: the input's BatchNorm applied while staging (in = the producer's z), or
-// null; bo: this conv's BatchNorm, whose per-(channel, sample) partials it leaves
-// and merges (kStatsOut), or null; bg: the input (= da) turned into this layer's
-// dz while staging (the BN backward), or null; gs: the BN-backward partials of the
-// layer whose da this conv writes, merged here, or null
-int launch_conv(const float *in, int cin, const float *wk, const float *bias, int cout, float *out, int B, bool acc,
-                hipStream_t st, const BnIn *bn = nullptr, const BnIn *bo = nullptr, const BnGrad *bg = nullptr,
-                const GradStats *gs = nullptr) {
-    const int cinp = round4(cin);
-    const size_t lds = ((size_t)cinp * kPlane + 2 * 2304 + (bn || bo || bg || gs ? kBnStatFloats + kLdsFlags : 0)) *
-                       sizeof(float);
-    const int a = acc ? 1 : 0;
-    const BnIn bn0{};
-    const BnGrad bg0{};
-    const GradStats gs0{};
-    const BnIn &b = bn ? *bn : bn0;
-    const BnIn &o = bo ? *bo : bn0;
-    const BnGrad &g = bg ? *bg : bg0;
-    const GradStats &s = gs ? *gs : gs0;
-    const int mode = (bn ? kBnIn : 0) | (bo ? kStatsOut : 0) | (bg ? kBnGrad : 0) | (gs ? kGradStats : 0);
-    // the hand-off counters are per channel slice
-    if ((bo || gs) && round16(cout) / 16 > kTickDbias) {
-        set_error("learner conv: %d output channels exceed the BatchNorm hand-off's slices", cout);
+    } else {
+        if (nt == 4) {
+            k_conv_mfma<CINP, 4><<<dim3(B), kThreads, lds, st>>>(in, cin, wk, bias, cout, 64, out, acc);
+            return SPAI_OK;
+        }
+        set_error("learner conv: %d input / %d output channels not built", cin, cout);
         return SPAI_ERR_UNSUPPORTED;
     }
-#define SPAI_CONV_CASE(C, M) \
-    case (C) * 16 + (M): return launch_conv_t<C, M>(B, lds, st, in, cin, wk, bias, cout, out, a, b, o, g, s);
-    switch (cinp * 16 + mode) {
-    SPAI_CONV_CASE(4, 0)
-    SPAI_CONV_CASE(4, kStatsOut)
-    SPAI_CONV_CASE(4, kGradStats)
-    SPAI_CONV_CASE(32, 0)
-    SPAI_CONV_CASE(64, 0)
-    SPAI_CONV_CASE(64, kStatsOut)
-    SPAI_CONV_CASE(64, kBnIn)
-    SPAI_CONV_CASE(64, kBnIn | kStatsOut)
-    SPAI_CONV_CASE(64, kBnGrad)
-    SPAI_CONV_CASE(64, kBnGrad | kGradStats)
-    default: set_error("learner conv: %d input channels (mode %d) not built", cin, mode); return SPAI_ERR_UNSUPPORTED;
-    }
-#undef SPAI_CONV_CASE
 }
 
-// dW (and db, when given) of one conv: chunk partials on f32 MFMA, then a fixed-order sum over the chunks
-int launch_wgrad(float *wpart, const float *x, int cin, const float *dz, int cout, int B, float *dw, hipStream_t st,
-                 float *db = nullptr) {
-    const int cinp = round4(cin), k1 = 9 * cinp + (db ? 1 : 0), nk = (k1 + 15) / 16, ntiles = (round16(cout) / 16) * nk;
+int launch_conv(const float *in, int cin, const float *wk, const float *bias, int cout, float *out, int B, bool acc,
+                hipStream_t st) {
+    const int a = acc ? 1 : 0;
+    switch (round4(cin)) {
+    case 4: return launch_conv_t<4>(B, st, in, cin, wk, bias, cout, out, a);
+    case 32: return launch_conv_t<32>(B, st, in, cin, wk, bias, cout, out, a);
+    case 64: return launch_conv_t<64>(B, st, in, cin, wk, bias, cout, out, a);
+    default: set_error("learner conv: %d input channels not built", cin); return SPAI_ERR_UNSUPPORTED;
+    }
+}
+
+// dW of one conv: chunk partials on f32 MFMA, then a fixed-order sum over the chunks
+int launch_wgrad(float *wpart, const float *x, int cin, const float *dz, int cout, int B, float *dw, hipStream_t st) {
+    const int cinp = round4(cin), k = 9 * cinp, nk = (k + 15) / 16, ntiles = (round16(cout) / 16) * nk;
     const int groups = std::max(1, (ntiles + 4 * kWgMaxTiles - 1) / (4 * kWgMaxTiles));
     const int chunks = (B + kWgSamples - 1) / kWgSamples;
-    const size_t lds = ((size_t)cinp * kPlane + (size_t)round16(cout) * 44 + (db ? kPlane : 0)) * sizeof(float);
+    const size_t lds = ((size_t)cinp * kPlane + (size_t)round16(cout) * 44) * sizeof(float);
     const dim3 grid(chunks, groups);
-    switch (cinp * 2 + (db ? 1 : 0)) {
-    case 4 * 2: k_wgrad_mfma<4, false><<<grid, kThreads, lds, st>>>(x, cin, dz, cout, B, groups, wpart); break;
-    case 64 * 2: k_wgrad_mfma<64, false><<<grid, kThreads, lds, st>>>(x, cin, dz, cout, B, groups, wpart); break;
-    case 64 * 2 + 1: k_wgrad_mfma<64, true><<<grid, kThreads, lds, st>>>(x, cin, dz, cout, B, groups, wpart); break;
+    switch (cinp) {
+    case 4: k_wgrad_mfma<4><<<grid, kThreads, lds, st>>>(x, cin, dz, cout, B, groups, wpart); break;
+    case 64: k_wgrad_mfma<64><<<grid, kThreads, lds, st>>>(x, cin, dz, cout, B, groups, wpart); break;
     default: set_error("learner wgrad: %d input channels not built", cin); return SPAI_ERR_UNSUPPORTED;
     }
-    k_wgrad_reduce<<<blocks_of((size_t)cout * k1, kWgReduceThreads), kWgReduceThreads, 0, st>>>(wpart, chunks, cin, cout,
-                                                                                               dw, db);
+    k_wgrad_reduce<<<blocks_of((size_t)cout * k, kWgReduceThreads), kWgReduceThreads, 0, st>>>(wpart, chunks, cin, cout,
+                                                                                              dw);
     return SPAI_OK;
 }
 
@@ -1335,8 +862,8 @@ void learner_destroy(spai_learner *L) {
     for (hipEvent_t ev : L->stage_ev)
         if (ev) (void)hipEventDestroy(ev);
     if (L->host_buf) (void)hipHostFree(L->host_buf);
-    for (auto *b : {&L->p, &L->g, &L->bsum, &L->m, &L->v, &L->wt, &L->batch_in, &L->d0, &L->d1, &L->d2, &L->dzb, &L->bn_part, &L->dlogits,
-                    &L->dpre, &L->loss_terms, &L->run_buf})
+    for (auto *b : {&L->p, &L->g, &L->bsum, &L->m, &L->v, &L->wt, &L->batch_in, &L->d0, &L->d1, &L->dlogits, &L->dpre,
+                    &L->loss_terms, &L->run_buf})
         b->release();
     L->run_idx.release();
     for (auto *vec : {&L->z, &L->a, &L->mean, &L->invstd})
@@ -1364,14 +891,6 @@ static int learner_allreduce(spai_learner *L, float *buf, size_t n, hipStream_t 
     return SPAI_OK;
 }
 
-// carved from the end of bn_part: the bias-gradient partials, then the counters
-static float *learner_db_part(spai_learner *L, uint32_t B) {
-    return L->bn_part.p + (size_t)(2 * L->blocks + 3) * L->hidden * B * 2;
-}
-static unsigned *learner_ticks(spai_learner *L, uint32_t B) {
-    return (unsigned *)(learner_db_part(L, B) + (size_t)L->hidden * B);
-}
-
 // Everything of one train step after the batch upload: gradients zeroed, weights
 // packed, forward, loss, backward (weight gradients on the side streams), the cross-rank
 // reduction when there is a communicator, Adam.  Launch-only (no host sync).
@@ -1383,8 +902,7 @@ int enqueue_step(spai_learner *L, uint32_t B, hipStream_t st, const float *x_in,
     // they got at learner_create
     const float eps = L->cfg.bn_eps, mom = L->cfg.bn_momentum;
     const size_t nl = L->convs.size();
-    k_pack_all<<<dim3(blocks_of((size_t)9 * 64 * 64), L->n_pack), kThreads, 0, st>>>(P, L->pack_desc.p, L->wt.p,
-                                                                                        learner_ticks(L, B));
+    k_pack_all<<<dim3(blocks_of((size_t)9 * 64 * 64), L->n_pack), kThreads, 0, st>>>(P, L->pack_desc.p, L->wt.p);
     const float *W = L->wt.p;
     const int pol = (int)nl - 2, val = (int)nl - 1;
 
@@ -1396,69 +914,17 @@ int enqueue_step(spai_learner *L, uint32_t B, hipStream_t st, const float *x_in,
         k_bn_fwd<<<c.co, kBn, 0, st>>>(L->z[l].p, c.co, (int)B, eps, mom, L->mean[l].p, L->invstd[l].p, P + c.mu,
                                        P + c.var, P + c.g, P + c.be, res, L->a[l].p);
     };
-    // default: a k_bn_fwd kernel after every conv.  SPAI_LEARNER_BN_FUSE=1 (measured
-    // variant, not the default): the trunk's BN + ReLU (+ residual) run inside the
-    // next conv's staging (BnIn), the statistics merged inside the producer conv --
-    // 150-172k samples/s against 190-196k (profiles/r05/learner): at B = 128 a conv
-    // is a ~11 us, latency-bound launch, and the in-launch hand-off's drain, ticket
-    // and merge (or, merged in the consumer's prologue, every workgroup's read of
-    // the B partials) cost more than the k_bn_fwd / k_bn_bwd launches they remove
-    static const bool fuse = [] {
-        const char *v = std::getenv("SPAI_LEARNER_BN_FUSE");
-        return v && std::atoi(v) != 0;
-    }();
-    const float *h = nullptr;
-    if (fuse) {
-        const int last = 2 * L->blocks;   // the trunk's last conv
-        auto part_of = [&](int l) { return (float2 *)L->bn_part.p + (size_t)l * L->hidden * B; };
-        // layer l's BN input to its consumer: the residual is the block input a[l - 2] for a block's second conv
-        unsigned *tick = learner_ticks(L, B);
-        auto bn_of = [&](int l) {
-            const spai_learner::Conv &c = L->convs[l];
-            const bool res = l >= 2 && l <= last && l % 2 == 0;
-            return BnIn{part_of(l), P + c.g, P + c.be, res ? L->a[l - 2].p : nullptr, L->a[l].p, L->mean[l].p,
-                        L->invstd[l].p, P + c.mu, P + c.var, (int)B, eps, mom, tick};
-        };
-        {
-            const spai_learner::Conv &c = L->convs[0];
-            const BnIn o = bn_of(0);
-            crc = launch_conv(x_in, c.ci, W + c.wk, P + c.b, c.co, L->z[0].p, (int)B, false, st, nullptr, &o);
-        }
-        for (int l = 1; l <= last && crc == SPAI_OK; ++l) {   // relu(h + BN(conv(relu(BN(conv(h)))))), model/mod.rs:152-165
-            const spai_learner::Conv &c = L->convs[l];
-            const BnIn b = bn_of(l - 1), o = bn_of(l);
-            crc = launch_conv(L->z[l - 1].p, c.ci, W + c.wk, P + c.b, c.co, L->z[l].p, (int)B, false, st, &b, &o);
-        }
-        if (crc == SPAI_OK) {   // the policy head conv applies the trunk's last BN and writes the trunk output
-            const spai_learner::Conv &c = L->convs[pol];
-            const BnIn b = bn_of(last), o = bn_of(pol);
-            crc = launch_conv(L->z[last].p, c.ci, W + c.wk, P + c.b, c.co, L->z[pol].p, (int)B, false, st, &b, &o);
-        }
-        h = L->a[last].p;
-        if (crc == SPAI_OK) {
-            const spai_learner::Conv &c = L->convs[val];
-            const BnIn o = bn_of(val);
-            crc = launch_conv(h, c.ci, W + c.wk, P + c.b, c.co, L->z[val].p, (int)B, false, st, nullptr, &o);
-        }
-        // the heads' BN + ReLU inside the loss kernel
-        k_heads_loss<true><<<B, kThreads, 0, st>>>(L->z[pol].p, L->z[val].p, P + L->pol_w, P + L->pol_b, P + L->val_w,
-                                                   P + L->val_b, pi_in, z_in, (int)B, L->dlogits.p, L->dpre.p,
-                                                   L->loss_terms.p, bn_of(pol), bn_of(val));
-    } else {
-        conv_bn_act(0, x_in, nullptr);
-        h = L->a[0].p;
-        for (int k = 0; k < L->blocks; ++k) {   // relu(h + BN(conv(relu(BN(conv(h)))))) (model/mod.rs:152-165)
-            conv_bn_act(1 + 2 * k, h, nullptr);
-            conv_bn_act(2 + 2 * k, L->a[1 + 2 * k].p, h);
-            h = L->a[2 + 2 * k].p;
-        }
-        conv_bn_act(pol, h, nullptr);
-        conv_bn_act(val, h, nullptr);
+    conv_bn_act(0, x_in, nullptr);
+    const float *h = L->a[0].p;
+    for (int k = 0; k < L->blocks; ++k) {   // relu(h + BN(conv(relu(BN(conv(h)))))) (model/mod.rs:152-165)
+        conv_bn_act(1 + 2 * k, h, nullptr);
+        conv_bn_act(2 + 2 * k, L->a[1 + 2 * k].p, h);
+        h = L->a[2 + 2 * k].p;
     }
-    if (!fuse)
-        k_heads_loss<false><<<B, kThreads, 0, st>>>(L->a[pol].p, L->a[val].p, P + L->pol_w, P + L->pol_b, P + L->val_w,
-                                                    P + L->val_b, pi_in, z_in, (int)B, L->dlogits.p, L->dpre.p,
-                                                    L->loss_terms.p, BnIn{}, BnIn{});
+    conv_bn_act(pol, h, nullptr);
+    conv_bn_act(val, h, nullptr);
+    k_heads_loss<<<B, kThreads, 0, st>>>(L->a[pol].p, L->a[val].p, P + L->pol_w, P + L->pol_b, P + L->val_w,
+                                         P + L->val_b, pi_in, z_in, (int)B, L->dlogits.p, L->dpre.p, L->loss_terms.p);
 
     // ---------------- backward
     // heads: linears -> relu/BN -> conv; dh (d0) = dgrad(policy) + dgrad(value)
@@ -1470,9 +936,7 @@ int enqueue_step(spai_learner *L, uint32_t B, hipStream_t st, const float *x_in,
     // its weight gradient on a side stream; nothing rewrites z[l] before the next step
     constexpr int kWgSide = spai_learner::kWgStreams;   // side streams the weight gradients rotate over
     int side = 0;
-    // dz: the layer's BN-backward output (z[l] overwritten by k_bn_bwd, or the fused
-    // path's dz buffer); db: the bias gradient from the weight gradient (fused path)
-    auto wgrad_async = [&](int l, const float *in, const float *dz = nullptr, float *db = nullptr) {
+    auto wgrad_async = [&](int l, const float *in) {
         const spai_learner::Conv &c = L->convs[l];
         if (crc != SPAI_OK) return;
         const int k = side++ % kWgSide;
@@ -1482,8 +946,7 @@ int enqueue_step(spai_learner *L, uint32_t B, hipStream_t st, const float *x_in,
             crc = SPAI_ERR_DEVICE;
             return;
         }
-        crc = launch_wgrad(L->wpart_side[k].p, in, c.ci, dz ? dz : L->z[l].p, c.co, (int)B, G + c.w, L->wg_stream[k],
-                           db);
+        crc = launch_wgrad(L->wpart_side[k].p, in, c.ci, L->z[l].p, c.co, (int)B, G + c.w, L->wg_stream[k]);
     };
     auto bn_conv_bwd = [&](int l, const float *da, const float *in, float *dx, bool acc, float *dy_out) {
         const spai_learner::Conv &c = L->convs[l];
@@ -1497,64 +960,6 @@ int enqueue_step(spai_learner *L, uint32_t B, hipStream_t st, const float *x_in,
                                                                 G + L->val_w, G + L->val_b);
     k_linear_bwd_x<<<blocks_of((size_t)B * 3 * kCells), kThreads, 0, st>>>(L->dpre.p, P + L->val_w, (int)B, 1,
                                                                             3 * kCells, L->d1.p);
-    // with the forward fusion on (SPAI_LEARNER_BN_FUSE=1), the trunk's BN backward runs in
-    // the data gradient's staging (BnGrad), its partials from the producer of da
-    // (GradStats), unless SPAI_LEARNER_BNB_FUSE=0 (a k_bn_bwd kernel before every data gradient)
-    static const bool bfuse = [] {
-        const char *v = std::getenv("SPAI_LEARNER_BNB_FUSE");
-        return !v || std::atoi(v) != 0;
-    }();
-    if (fuse && bfuse) {
-        const int last = 2 * L->blocks;
-        auto gpart_of = [&](int l) { return (float2 *)L->bn_part.p + (size_t)l * L->hidden * B; };
-        auto dzb_of = [&](int l) { return L->dzb.p + (size_t)(l - 1) * B * L->hidden * kCells; };   // l >= 1
-        unsigned *tick = learner_ticks(L, B);
-        float *db_part = learner_db_part(L, B);
-        auto gs_of = [&](int l) {
-            const spai_learner::Conv &c = L->convs[l];
-            return GradStats{L->a[l].p, L->z[l].p, L->mean[l].p, L->invstd[l].p, gpart_of(l), G + c.g, G + c.be, tick};
-        };
-        auto bg_of = [&](int l, float *dy_out) {
-            const spai_learner::Conv &c = L->convs[l];
-            return BnGrad{L->a[l].p, L->z[l].p, L->mean[l].p, L->invstd[l].p, P + c.g, G + c.g, G + c.be, dzb_of(l),
-                          dy_out, db_part, G + c.b, tick, (int)B};
-        };
-        {   // value head: its BN backward as before; its data gradient completes dL/d(trunk output)
-            const spai_learner::Conv &c = L->convs[val];
-            k_bn_bwd<<<c.co, kBn, 0, st>>>(L->d1.p, L->a[val].p, L->z[val].p, c.co, (int)B, L->mean[val].p,
-                                           L->invstd[val].p, P + c.g, G + c.g, G + c.be, G + c.b, L->z[val].p, nullptr);
-            wgrad_async(val, h);
-            const GradStats g = gs_of(last);
-            if (crc == SPAI_OK)
-                crc = launch_conv(L->z[val].p, c.co, W + c.wkd, nullptr, c.ci, L->d0.p, (int)B, true, st, nullptr,
-                                  nullptr, nullptr, last > 0 ? &g : nullptr);
-        }
-        float *X = L->d0.p, *Y = L->d1.p, *T = L->d2.p;   // dL/d(block output), dL/d(relu1 output), skip + block input
-        for (int k = L->blocks - 1; k >= 0 && crc == SPAI_OK; --k) {
-            const int l1 = 1 + 2 * k, l2 = 2 + 2 * k;
-            const float *hin = L->a[l1 - 1].p;
-            {   // conv 2: dz from X (dy = the skip gradient -> T), dx -> Y, the partials of conv 1's BN
-                const spai_learner::Conv &c = L->convs[l2];
-                const BnGrad bgv = bg_of(l2, T);
-                const GradStats g = gs_of(l1);
-                crc = launch_conv(X, c.co, W + c.wkd, nullptr, c.ci, Y, (int)B, false, st, nullptr, nullptr, &bgv, &g);
-                wgrad_async(l2, L->a[l1].p, dzb_of(l2));
-            }
-            if (crc == SPAI_OK) {   // conv 1: dz from Y, dx accumulated into T = dL/d(block input)
-                const spai_learner::Conv &c = L->convs[l1];
-                const BnGrad bgv = bg_of(l1, nullptr);
-                const GradStats g = gs_of(l1 - 1);
-                crc = launch_conv(Y, c.co, W + c.wkd, nullptr, c.ci, T, (int)B, true, st, nullptr, nullptr, &bgv,
-                                  l1 - 1 > 0 ? &g : nullptr);
-                wgrad_async(l1, hin, dzb_of(l1));
-            }
-            float *nx = T;
-            T = Y;
-            Y = X;
-            X = nx;
-        }
-        bn_conv_bwd(0, X, x_in, nullptr, false, nullptr);   // stem: no data gradient
-    } else {
     bn_conv_bwd(val, L->d1.p, h, L->d0.p, true, nullptr);
     // residual blocks in reverse; d0 holds dL/d(block output)
     for (int k = L->blocks - 1; k >= 0; --k) {
@@ -1571,7 +976,6 @@ int enqueue_step(spai_learner *L, uint32_t B, hipStream_t st, const float *x_in,
     }
     // stem: no data gradient
     bn_conv_bwd(0, L->d0.p, x_in, nullptr, false, nullptr);
-    }
     // join: every weight gradient is in G before the reduction and Adam
     for (int k = 0; k < kWgSide && crc == SPAI_OK; ++k)
         if (hipEventRecord(L->ev_wg_done[k], L->wg_stream[k]) != hipSuccess ||

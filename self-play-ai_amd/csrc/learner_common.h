@@ -9,7 +9,7 @@
 // (train_batch), the parameter-layout record (Conv, Layout), and the kernels that
 // are the same in both: the workgroup reductions, train-mode BatchNorm forward and
 // ReLU + BatchNorm backward (templated on the cells of a plane: 9, 64) and Adam.
-// The Connect4 learner keeps its own fused kernels and state (spai_learner).
+// The Connect4 learner keeps its own kernels and state (spai_learner).
 #pragma once
 #include <algorithm>
 #include <cmath>

@@ -87,7 +87,7 @@ ADAM_CASES = [
 # (game, blocks, B): config B, two steps, trained-like start; (connect4, 1, 150) is past
 # the 146 samples whose 6144 values per channel k_bn_fwd keeps in registers
 BN_CASES = [("tictactoe", 1, 5), ("chess", 1, 5), ("connect4", 1, 5), ("connect4", 1, 150)]
-BN_FUSED_CASE = ("connect4", 2, 8)   # SPAI_LEARNER_BN_FUSE=1, one step
+BN_ONE_STEP_CASE = ("connect4", 2, 8)   # two residual blocks, one step
 BN_STEPS = 2
 PROJECT = dict(loss=1e-4, loss_later=1e-3, grad=3e-4, run_rtol=1e-4, run_atol=1e-5)
 

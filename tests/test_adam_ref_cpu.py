@@ -48,7 +48,7 @@ Measured here (the synthetic run: 10^5 entries, p ~ N(0, 0.4), 12 steps):
     (connect4,  2,   8)   1.9e+04       4.2e+03           205
 
     PyTorch CPU fp32 against the float64 restatement at config B, every step from the
-    same parameters, two steps (one for the fused case (connect4, 2, 8)): loss
+    same parameters, two steps (one for the one-step case (connect4, 2, 8)): loss
     (relative), gradient / max|g|, running statistics in units of rtol 1e-4 + atol
     1e-5.  The project's bars are 1e-4 (1e-3 later), 3e-4 and 1; every figure is under a
     third of its bar, so all of them stand (optimizer_cases.MEASURED_B, bn_bars):
@@ -226,7 +226,7 @@ def test_learner_inputs_stay_under_the_mask_limit(game, blocks, B, name, steps, 
 
 
 # ------------------------------------------------------------------ BatchNorm settings: visible, and the bars
-ALL_BN = OC.BN_CASES + [OC.BN_FUSED_CASE]
+ALL_BN = OC.BN_CASES + [OC.BN_ONE_STEP_CASE]
 
 
 @pytest.mark.parametrize("game,blocks,B", ALL_BN)
@@ -278,7 +278,7 @@ def test_fp32_distance_at_config_b(game, blocks, B):
     """the figures behind optimizer_cases.MEASURED_B, live: a figure may not leave the
     table (beyond 2 x, or a thirtieth of its bar where the table's figure is tiny), so
     bn_bars keeps deciding from what this CPU measures"""
-    steps = 1 if (game, blocks, B) == OC.BN_FUSED_CASE else OC.BN_STEPS
+    steps = 1 if (game, blocks, B) == OC.BN_ONE_STEP_CASE else OC.BN_STEPS
     p0 = OC.start(game, blocks)
     _, n, tr = OC.layout(game, blocks)
     batches = OC.cpu_batches(game, B, steps, OC.seed_of(game, blocks, B))

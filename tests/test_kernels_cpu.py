@@ -60,3 +60,34 @@ def test_no_compile_time_variants_in_kernels():
                 if not macro.startswith("SPAI_DIAG"):
                     bad.append("%s:%d: %s" % (os.path.basename(path), no, macro))
     assert not bad, bad
+
+
+def test_c4_learner_builds_only_the_kernels_it_launches(descriptors):
+    """The Connect4 train step has one path, and learner.hip instantiates exactly what
+    that path can launch: k_conv_mfma<4,4> (the stem), <32,1> and <64,1> (launch_conv's
+    three-way dispatch on the padded input channels), k_wgrad_mfma<4> and <64>, and one
+    k_heads_loss.  An instantiation that no launch reaches is dead weight in the code
+    object (at one time two thirds of the learner's .text)."""
+    import re
+
+    def tails(kernel):   # the mangled template arguments (and parameters) after the kernel's name
+        return sorted(m.group(1) for m in (re.search(r"\d+%s(\w*)$" % kernel, n) for n in descriptors) if m)
+
+    conv, wgrad, heads = tails("k_conv_mfma"), tails("k_wgrad_mfma"), tails("k_heads_loss")
+    assert [t.split("EE")[0] for t in conv] == ["ILi32ELi1", "ILi4ELi4", "ILi64ELi1"], conv
+    assert [t.split("EE")[0] for t in wgrad] == ["ILi4", "ILi64"], wgrad
+    assert len(heads) == 1, heads
+
+
+def test_every_environment_knob_is_documented():
+    """every "SPAI_..." string literal of the library's sources (a getenv name) has its
+    row in INTEGRATION.md's "Environment knobs" section"""
+    import glob
+    import re
+    doc = open(os.path.join(REPO, "INTEGRATION.md")).read()
+    section = doc.split("## Environment knobs", 1)[1].split("\n## ", 1)[0]
+    files = sorted(glob.glob(os.path.join(REPO, "self-play-ai_amd", "csrc", "*")))
+    names = {m for path in files if os.path.isfile(path) for m in re.findall(r'"(SPAI_\w+)"', open(path).read())}
+    assert "SPAI_TRACE_MOVES" in names   # the scan finds the literals
+    missing = sorted(n for n in names if not re.search(r"\b%s\b" % n, section))
+    assert not missing, missing

@@ -38,7 +38,6 @@ contracted), tier 1 sits at <= 0.17 x the bar, float32(1 - 0.9^t) is exactly 1 f
 step 165, and no device gradient put an entry into the subnormal mask.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -252,36 +251,22 @@ def test_bn_settings_vs_restatement(spai, st, sc, game, blocks, B):
     G.close()
 
 
-def test_bn_settings_fused_path(spai, st, sc, tmp_path):
-    """SPAI_LEARNER_BN_FUSE=1 (read once per process, hence the subprocess): BnIn carries
-    eps and the momentum inside the neighbouring convs.  Connect4 (2, 8), config B, one
-    step, the same bars against the same restatement"""
-    import subprocess
-    import sys
-    from conftest import REPO
-    game, blocks, B = OC.BN_FUSED_CASE
+def test_bn_settings_one_step(spai, st, sc):
+    """Connect4 (2, 8), config B, one step from the trained-like start: two residual
+    blocks at a batch between BN_CASES' 5 and 150, the same bars against the same
+    restatement"""
+    game, blocks, B = OC.BN_ONE_STEP_CASE
     G = _Game(game, spai, st, sc)
     batch, = G.batches(B, 1, OC.seed_of(game, blocks, B))
-    G.close()
     p0 = OC.start(game, blocks)
-    nl = OC.restatement(game)[2](blocks)
-    np.savez(tmp_path / "in.npz", x=batch[0], pi=batch[1], z=batch[2], p0=p0)
-    code = (
-        "import sys, numpy as np; sys.path.insert(0, %r); import spai\n"
-        "d = np.load(%r); e = spai.Engine(num_searches=1, max_trees=1)\n"
-        "L = spai.Learner(e, %d, d['p0'], **%r)\n"
-        "loss = L.train_batch(d['x'], d['pi'], d['z'])\n"
-        "np.savez(sys.argv[1], loss=loss, g=L.grads(), p=L.params(), **{'a%%d' %% l: L.activation(l) > 0 for l in range(%d)})\n"
-        % (os.path.join(REPO, "self-play-ai_amd"), str(tmp_path / "in.npz"), blocks, AR.CONFIG_B, nl))
-    f = str(tmp_path / "out.npz")
-    r = subprocess.run([sys.executable, "-c", code, f], env=dict(os.environ, SPAI_LEARNER_BN_FUSE="1"),
-                       capture_output=True, text=True, timeout=240)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = np.load(f)
     _, n, tr = OC.layout(game, blocks)
-    masks = [out["a%d" % l] for l in range(nl)]
-    _check_bn_step(game, OC.BN_FUSED_CASE, 1, p0, batch, blocks, masks, out["loss"], out["g"], out["p"], tr)
-    AR.check_adam_steps(lambda k: (out["g"], out["p"]), p0, tr, AR.CONFIG_B, 1)
+    L = G.learner(blocks, p0, AR.CONFIG_B)
+    loss = L.train_batch(*batch)
+    g, P = L.grads(), L.params()
+    _check_bn_step(game, OC.BN_ONE_STEP_CASE, 1, p0, batch, blocks, G.masks(L, blocks), loss, g, P, tr)
+    AR.check_adam_steps(lambda k: (g, P), p0, tr, AR.CONFIG_B, 1)
+    L.close()
+    G.close()
 
 
 # ------------------------------------------------------------------ validation
