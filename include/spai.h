@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define SPAI_VERSION_MAJOR 0
-#define SPAI_VERSION_MINOR 4
+#define SPAI_VERSION_MINOR 5
 
 typedef enum spai_error {
     SPAI_OK = 0,
@@ -688,6 +688,34 @@ int spai_chess_tree_root(spai_chess *e, uint32_t tree, spai_chess_state *root, u
  * reps[i] = get_status / get_num_repetitions of the new root (either may be NULL) */
 int spai_chess_trees_advance(spai_chess *e, uint32_t n, const uint32_t *tree_idx, const uint32_t *child_index,
                              uint8_t *status, uint32_t *reps);
+
+/* Root exploration noise (AlphaZero's Dirichlet noise; the reference leaves it open,
+ * mcts.rs:204-207).  OPT-IN: an engine is created with epsilon = 0 and then searches
+ * exactly as the reference does, launching nothing more than before.  With epsilon > 0,
+ * every keyed search call (spai_chess_search_keyed, and the searches of
+ * spai_chess_selfplay_run / _stream / _compact) mixes each searched tree's root priors
+ * once, before the call's first selection at that root:
+ *     P_j <- (1 - epsilon) * P_j + epsilon * eta_j,  eta ~ Dirichlet(alpha, ..., alpha)
+ * over the root's children j in stored (MoveGen) order, in float32 with 1 - epsilon
+ * rounded once and each product and the sum rounded on their own; no renormalisation
+ * (both vectors sum to 1 up to rounding).  Only the children's prior words are written.
+ * eta is a function of (cfg.seed, game id, move number, number of children, alpha)
+ * alone -- the keys of self-play's move draw, under a Philox key of its own -- so a
+ * game does not depend on how games are batched, windowed or sharded.  The mix is
+ * stored in the tree: a root searched twice without a move in between is mixed twice.
+ * spai_chess_search and spai_chess_match_run NEVER apply noise, whatever is set here.
+ * epsilon = 0 (default): off.  alpha in [0.01, 100], epsilon in [0, 1], else SPAI_ERR_INVALID */
+int spai_chess_set_root_noise(spai_chess *e, float alpha, float epsilon);
+int spai_chess_get_root_noise(spai_chess *e, float *alpha, float *epsilon);
+/* the draws themselves, by the search's own device function: eta [count][SPAI_CHESS_MAX_MOVES],
+ * entries >= n_children[i] zero; n_children[i] in [1, 218]; seed = cfg.seed */
+int spai_chess_root_noise(spai_chess *e, uint32_t count, const uint64_t *game_id, const uint32_t *move_no,
+                          const uint32_t *n_children, float alpha, float *eta);
+/* spai_chess_search with root noise keyed per tree (engine's alpha / epsilon; epsilon 0 = plain search);
+ * with epsilon > 0 a tree may be listed once only */
+int spai_chess_search_keyed(spai_chess *e, uint32_t n, const uint32_t *tree_idx, const uint64_t *game_id,
+                            const uint32_t *move_no, uint32_t num_searches, float *policy, uint32_t *child_ids,
+                            float *child_visits, uint16_t *child_moves, uint32_t *n_children);
 
 /* SelfPlayWorker::self_play (learner_concurrent.rs:169-242) for chess */
 typedef void (*spai_chess_sample_sink)(void *user, uint32_t game_id, uint32_t n,

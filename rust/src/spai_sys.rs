@@ -281,6 +281,14 @@ extern "C" {
     pub fn spai_chess_search(e: *mut spai_chess, n: u32, tree_idx: *const u32, num_searches: u32, policy: *mut f32,
                              child_ids: *mut u32, child_visits: *mut f32, child_moves: *mut u16,
                              n_children: *mut u32) -> c_int;
+    // Dirichlet root noise, opt-in (epsilon 0 = off: the reference's search); keyed searches and self-play only
+    pub fn spai_chess_set_root_noise(e: *mut spai_chess, alpha: f32, epsilon: f32) -> c_int;
+    pub fn spai_chess_get_root_noise(e: *mut spai_chess, alpha: *mut f32, epsilon: *mut f32) -> c_int;
+    pub fn spai_chess_root_noise(e: *mut spai_chess, count: u32, game_id: *const u64, move_no: *const u32,
+                                 n_children: *const u32, alpha: f32, eta: *mut f32) -> c_int;
+    pub fn spai_chess_search_keyed(e: *mut spai_chess, n: u32, tree_idx: *const u32, game_id: *const u64,
+                                   move_no: *const u32, num_searches: u32, policy: *mut f32, child_ids: *mut u32,
+                                   child_visits: *mut f32, child_moves: *mut u16, n_children: *mut u32) -> c_int;
     pub fn spai_chess_tree_use_subtree(e: *mut spai_chess, tree: u32, child_index: u32) -> c_int;
     pub fn spai_chess_tree_children(e: *mut spai_chess, tree: u32, moves: *mut u16, visits: *mut u32,
                                     n: *mut u32) -> c_int;

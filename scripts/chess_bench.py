@@ -57,6 +57,9 @@ def parse():
     ap.add_argument("--stream", action="store_true",
                     help="--full: the K x games games through `games` tree slots (spai_chess_selfplay_stream)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--root-noise", type=float, nargs=2, metavar=("ALPHA", "EPS"), default=None,
+                    help="Dirichlet root noise (ChessEngine.set_root_noise); the default window then searches "
+                         "keyed by (game, move).  Default: off, the reference's search")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--cpu-games", type=int, default=32)
@@ -167,6 +170,8 @@ def main():
     eng.trees_create(args.games)
     eng.search(np.arange(args.games), num_searches=4)
     eng.trees_create(args.games)
+    if args.root_noise is not None:
+        eng.set_root_noise(*args.root_noise)
     eng.set_timing(True)
     stop = threading.Event()
     t_start = time.perf_counter()
@@ -187,7 +192,8 @@ def main():
         sims = games = moves = 0
         t0 = time.perf_counter()
         for m in range(args.moves):
-            pol, ids, vis, mv, nc = eng.search(live)
+            keys = None if args.root_noise is None else (live, np.full(len(live), m, np.uint32))
+            pol, ids, vis, mv, nc = eng.search(live, noise_keys=keys)
             sims += len(live) * args.sims
             w = np.power(vis.astype(np.float64), 1.25)          # learner_concurrent.rs:189-193
             w[np.arange(vis.shape[1])[None, :] >= nc[:, None]] = 0
@@ -223,7 +229,8 @@ def main():
                                   ("%d games to completion%s" % (args.batches * args.games,
                                                                  ", streamed through the slots" if args.stream else "")
                                    if args.full else "first %d moves" % moves)),
-                   "games": args.games, "sims_per_move": args.sims, "blocks": args.blocks},
+                   "games": args.games, "sims_per_move": args.sims, "blocks": args.blocks,
+                   "root_noise": args.root_noise},
         "seconds": dt, "moves": moves, "games_finished": games,
         "games_per_sec": games / dt if args.full else None,
         "kernel_ms": {"select_leaf": ms[0], "forward": ms[1], "expand": ms[2]},

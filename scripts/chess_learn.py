@@ -295,7 +295,8 @@ def learn(args):
     cfg = dict(num_learn_iters=args.iters, num_self_play_iters=args.self_play_iters,
                num_parallel_self_play_games=args.games, batch_size=args.batch, num_epochs=args.epochs,
                num_searches=args.sims, blocks=args.blocks, seed=args.seed, clone_self_play=not args.distinct,
-               window=args.window, compute=args.compute, samples=args.samples)
+               window=args.window, compute=args.compute, samples=args.samples,
+               root_noise=tuple(args.root_noise) if args.root_noise else None)
     with tempfile.TemporaryDirectory() as d:
         t0 = time.perf_counter()
         rec = sc.learn(checkpoint_dir=d, **cfg)
@@ -337,6 +338,8 @@ def main():
     ap.add_argument("--self-play-iters", type=int, default=2)
     ap.add_argument("--distinct", action="store_true", help="clone_self_play=False")
     ap.add_argument("--window", type=int, default=None, help="--learn: self-play through this many tree slots")
+    ap.add_argument("--root-noise", type=float, nargs=2, metavar=("ALPHA", "EPS"), default=None,
+                    help="--learn: Dirichlet noise at the self-play roots (default: off, the reference's search)")
     ap.add_argument("--sims", type=int, default=16)
     ap.add_argument("--blocks", type=int, default=2)
     ap.add_argument("--batch", type=int, default=32)

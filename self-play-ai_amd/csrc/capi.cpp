@@ -93,7 +93,7 @@ extern "C" {
 
 const char *spai_last_error(void) { return g_err; }
 
-const char *spai_version(void) { return "spai 0.4 (gfx950)"; }
+const char *spai_version(void) { return "spai 0.5 (gfx950)"; }
 
 int spai_device_count(int *count) {
     SPAI_PTR(count);

@@ -57,6 +57,9 @@ void release_all(spai_chess *e) {
     B.logits.release();
     B.value.release();
     e->active.release();
+    e->noise_gid.release();
+    e->noise_move.release();
+    e->noise_done.release();
     e->err.release();
     match_release(e);
     for (hipEvent_t ev : e->timer.ev) (void)hipEventDestroy(ev);
@@ -294,6 +297,49 @@ int spai_chess_search(spai_chess *e, uint32_t n, const uint32_t *tree_idx, uint3
     CH_CHECK(e);
     SPAI_PTR(tree_idx);
     return search(e, n, tree_idx, num_searches, policy, child_ids, child_visits, child_moves, n_children, nullptr);
+}
+
+int spai_chess_set_root_noise(spai_chess *e, float alpha, float epsilon) {
+    CH_CHECK(e);
+    SPAI_CHECK(alpha >= 0.01f && alpha <= 100.0f, SPAI_ERR_INVALID, "root noise: alpha %g not in [0.01, 100]",
+               (double)alpha);
+    SPAI_CHECK(epsilon >= 0.0f && epsilon <= 1.0f, SPAI_ERR_INVALID, "root noise: epsilon %g not in [0, 1]",
+               (double)epsilon);
+    e->noise_alpha = alpha;
+    e->noise_eps = epsilon;
+    return SPAI_OK;
+}
+
+int spai_chess_get_root_noise(spai_chess *e, float *alpha, float *epsilon) {
+    CH_CHECK(e);
+    if (alpha) *alpha = e->noise_alpha;
+    if (epsilon) *epsilon = e->noise_eps;
+    return SPAI_OK;
+}
+
+int spai_chess_root_noise(spai_chess *e, uint32_t count, const uint64_t *game_id, const uint32_t *move_no,
+                          const uint32_t *n_children, float alpha, float *eta) {
+    CH_CHECK(e);
+    SPAI_CHECK(alpha >= 0.01f && alpha <= 100.0f, SPAI_ERR_INVALID, "root noise: alpha %g not in [0.01, 100]",
+               (double)alpha);
+    if (count) {
+        SPAI_PTR(game_id);
+        SPAI_PTR(move_no);
+        SPAI_PTR(n_children);
+        SPAI_PTR(eta);
+    }
+    return root_noise_draws(e, count, game_id, move_no, n_children, alpha, eta);
+}
+
+int spai_chess_search_keyed(spai_chess *e, uint32_t n, const uint32_t *tree_idx, const uint64_t *game_id,
+                            const uint32_t *move_no, uint32_t num_searches, float *policy, uint32_t *child_ids,
+                            float *child_visits, uint16_t *child_moves, uint32_t *n_children) {
+    CH_CHECK(e);
+    SPAI_PTR(tree_idx);
+    SPAI_PTR(game_id);
+    SPAI_PTR(move_no);
+    return search(e, n, tree_idx, num_searches, policy, child_ids, child_visits, child_moves, n_children, nullptr,
+                  game_id, move_no);
 }
 
 int spai_chess_tree_reset(spai_chess *e, uint32_t tree, uint32_t slot) {

@@ -99,6 +99,11 @@ struct spai_chess {
     spai::chess::Batch batch;
     spai::DevBuf<uint32_t> active;   // active tree list
     spai::DevBuf<uint32_t> err;      // device error flags
+    // Dirichlet root noise (spai_chess_set_root_noise); epsilon 0 = off.  Per entry of `active`:
+    // the tree's game id and move number, and whether its root was noised in the current call
+    float noise_alpha = 0.3f, noise_eps = 0.0f;
+    spai::DevBuf<uint64_t> noise_gid;
+    spai::DevBuf<uint32_t> noise_move, noise_done;
     spai_chess_net *net = nullptr;
     spai::KernelTimer timer;
     spai::chess::MatchBufs match;
@@ -170,8 +175,13 @@ int net_image(spai_chess_net *net, void *out, size_t cap, size_t *bytes);
 
 // chess_search.hip
 int trees_create(spai_chess *e, uint32_t n);
+// game_id / move_no [n] (both or neither): the trees' root-noise keys, read when the engine's epsilon > 0
 int search(spai_chess *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, float *policy,
-           uint32_t *child_ids, float *child_visits, uint16_t *child_moves, uint32_t *n_children, double *evals);
+           uint32_t *child_ids, float *child_visits, uint16_t *child_moves, uint32_t *n_children, double *evals,
+           const uint64_t *game_id = nullptr, const uint32_t *move_no = nullptr);
+// the Dirichlet draws of the given keys by the search's own device function: eta [count][kMaxMoves]
+int root_noise_draws(spai_chess *e, uint32_t count, const uint64_t *game_id, const uint32_t *move_no,
+                     const uint32_t *n_children, float alpha, float *eta);
 int tree_use_subtree(spai_chess *e, uint32_t tree, uint32_t child_index);
 int tree_reset_from_slot(spai_chess *e, uint32_t tree, uint32_t slot);
 int tree_root(spai_chess *e, uint32_t tree, spai_chess_state *root, uint32_t *visits, float *value_sum);

@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "chess_search_internal.h"
+#include "dirichlet.h"
 #include "philox.h"
 
 namespace spai {
@@ -369,6 +370,59 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_ccompact(TV T, const ui
     }
 }
 
+// Dirichlet root noise (dirichlet.h), once per tree per search call: the prior word of
+// every root child becomes (1 - eps) * P + eps * eta, eta drawn under the tree's key
+// (gid[gi], move[gi]); no other field and no other node is written, no renormalisation.
+// Launched twice per call.  entry = 1 (after k_ccompact, before iteration 0): the trees
+// whose root already has children are mixed, and done[gi] records for every tree whether
+// it was.  entry = 0 (after iteration 0): the trees not mixed yet whose root iteration 0
+// expanded.  A root that stays without children (a finished game) is never mixed.
+__global__ __launch_bounds__(64 * kWavesPerBlock) void k_croot_noise(TV T, const uint32_t *__restrict__ active,
+                                                                    uint32_t n_active,
+                                                                    const uint64_t *__restrict__ gid,
+                                                                    const uint32_t *__restrict__ move, uint32_t *done,
+                                                                    int entry, uint64_t seed, float alpha,
+                                                                    float one_minus_eps, float eps) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t gi = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (gi >= n_active) return;
+    if (!entry && done[gi]) return;
+    const uint32_t t = active[gi];
+    const size_t base = tbase(T, t);
+    const uint32_t r = T.root[t];
+    const uint32_t nch = T.nodes[base + r].w >> 16;
+    if (nch == 0 || nch > (uint32_t)kMaxChildren) {
+        if (entry && lane == 0) done[gi] = 0;
+        return;
+    }
+    const uint32_t f = T.first[base + r];
+    float eta[4];
+    wave_dirichlet(seed, gid[gi], move[gi], nch, alpha, lane, eta);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t j = (uint32_t)lane + 64u * k;
+        if (j < nch) {
+            uint32_t *rec = (uint32_t *)(T.nodes + base + f + j);
+            rec[2] = __float_as_uint(dirichlet_mix(__uint_as_float(rec[2]), eta[k], one_minus_eps, eps));
+        }
+    }
+    if (lane == 0) done[gi] = 1;
+}
+
+// spai_chess_root_noise: the draws themselves, one wave per key; eta [count][kMaxMoves], zero past n[i]
+__global__ __launch_bounds__(64 * kWavesPerBlock) void k_cnoise_draws(uint32_t count, const uint64_t *__restrict__ gid,
+                                                                     const uint32_t *__restrict__ move,
+                                                                     const uint32_t *__restrict__ n, uint64_t seed,
+                                                                     float alpha, float *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t i = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (i >= count) return;
+    float eta[4];
+    wave_dirichlet(seed, gid[i], move[i], n[i], alpha, lane, eta);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out[(size_t)i * kMaxMoves + lane + 64 * k] = eta[k];
+}
+
 // every tree t < n (list null), or the n trees list[i], as a one-node tree at the start position
 __global__ void k_ctrees_init(TV T, uint32_t n, const uint32_t *__restrict__ list) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -578,6 +632,9 @@ int trees_create(spai_chess *e, uint32_t n) {
         SPAI_TRY(B.logits.alloc((size_t)n * kPolicy));
         SPAI_TRY(B.value.alloc(n));
         SPAI_TRY(e->active.alloc(n));
+        SPAI_TRY(e->noise_gid.alloc(n));
+        SPAI_TRY(e->noise_move.alloc(n));
+        SPAI_TRY(e->noise_done.alloc(n));
     }
     k_ctrees_init<<<(n + 255) / 256, 256, 0, e->stream>>>(view(e), n, nullptr);
     SPAI_HIP(hipGetLastError());
@@ -616,6 +673,18 @@ int chain_launch(spai_chess *e, const Chain &C) {
     }
     k_ccompact<<<blocks_for(na), 64 * kWavesPerBlock, 0, C.stream>>>(T, C.active, na, sims * kMaxChildren, C.err);
     SPAI_HIP(hipGetLastError());
+    const bool noise = C.noise_eps > 0.0f;
+    SPAI_CHECK(!noise || (C.noise_gid && C.noise_move && C.noise_done), SPAI_ERR_INVALID,
+               "internal: root noise without its key arrays");
+    auto root_noise = [&](int entry) -> int {
+        k_croot_noise<<<blocks_for(na), 64 * kWavesPerBlock, 0, C.stream>>>(T, C.active, na, C.noise_gid, C.noise_move,
+                                                                           C.noise_done, entry, C.noise_seed,
+                                                                           C.noise_alpha, 1.0f - C.noise_eps,
+                                                                           C.noise_eps);
+        SPAI_HIP(hipGetLastError());
+        return SPAI_OK;
+    };
+    if (noise) SPAI_TRY(root_noise(1));   // behind the compaction, which moves the root's children
     KernelTimer *tm = C.timer;
     auto stamp = [&](int which, bool begin) -> int {
         if (tm->used >= tm->ev.size()) {
@@ -643,6 +712,8 @@ int chain_launch(spai_chess *e, const Chain &C) {
         k_cexpand<<<blocks_for(na), 64 * kWavesPerBlock, 0, C.stream>>>(T, BVv, na, cnt, kind, C.err);
         SPAI_HIP(hipGetLastError());
         if (timed) SPAI_TRY(stamp(2, false));
+        // a root without children on entry was expanded by iteration 0, with no selection at it yet
+        if (noise && it == 0) SPAI_TRY(root_noise(0));
     }
     return SPAI_OK;
 }
@@ -686,9 +757,25 @@ int chain_finish(spai_chess *e, const Chain &C, double *evals_out) {
 }
 
 namespace {
-// the engine's own chain over e->active[0, na): self-play's and spai_chess_search's search
-int run_search(spai_chess *e, uint32_t na, uint32_t sims, double *evals_out) {
-    const Chain C = engine_chain(e, na, sims);
+// the keys of the trees in e->active[0, na), uploaded next to it: only a search with root noise reads them
+int upload_noise_keys(spai_chess *e, uint32_t na, const uint64_t *gid, const uint32_t *move) {
+    SPAI_HIP(hipMemcpyAsync(e->noise_gid.p, gid, 8ull * na, hipMemcpyHostToDevice, e->stream));
+    SPAI_HIP(hipMemcpyAsync(e->noise_move.p, move, 4ull * na, hipMemcpyHostToDevice, e->stream));
+    return SPAI_OK;
+}
+
+// the engine's own chain over e->active[0, na): self-play's and spai_chess_search's search.
+// keyed: with the engine's root noise (if its epsilon > 0), the trees' keys already uploaded
+int run_search(spai_chess *e, uint32_t na, uint32_t sims, double *evals_out, bool keyed = false) {
+    Chain C = engine_chain(e, na, sims);
+    if (keyed && e->noise_eps > 0.0f) {
+        C.noise_eps = e->noise_eps;
+        C.noise_alpha = e->noise_alpha;
+        C.noise_seed = e->cfg.seed;
+        C.noise_gid = e->noise_gid.p;
+        C.noise_move = e->noise_move.p;
+        C.noise_done = e->noise_done.p;
+    }
     SPAI_TRY(chain_launch(e, C));
     return chain_finish(e, C, evals_out);
 }
@@ -724,7 +811,8 @@ void dense_policy(int side, uint32_t nch, const uint32_t *vis, const uint16_t *m
 }
 
 int search(spai_chess *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, float *policy,
-           uint32_t *child_ids, float *child_visits, uint16_t *child_moves, uint32_t *n_children, double *evals) {
+           uint32_t *child_ids, float *child_visits, uint16_t *child_moves, uint32_t *n_children, double *evals,
+           const uint64_t *game_id, const uint32_t *move_no) {
     Trees &Tr = e->trees;
     SPAI_CHECK(Tr.n > 0, SPAI_ERR_INVALID, "no trees (spai_chess_trees_create)");
     SPAI_CHECK(n >= 1 && n <= Tr.n, SPAI_ERR_INVALID, "search: n=%u trees (have %u)", n, Tr.n);
@@ -733,7 +821,17 @@ int search(spai_chess *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_sea
     for (uint32_t i = 0; i < n; ++i)
         SPAI_CHECK(tree_idx[i] < Tr.n, SPAI_ERR_INVALID, "tree index %u out of range", tree_idx[i]);
     SPAI_HIP(hipMemcpyAsync(e->active.p, tree_idx, 4 * n, hipMemcpyHostToDevice, e->stream));
-    SPAI_TRY(run_search(e, n, num_searches, evals));
+    const bool keyed = game_id && move_no && e->noise_eps > 0.0f;
+    if (keyed) {
+        // a tree listed twice would be mixed twice in one call, by two waves at once
+        std::vector<char> seen(Tr.n, 0);
+        for (uint32_t i = 0; i < n; ++i) {
+            SPAI_CHECK(!seen[tree_idx[i]], SPAI_ERR_INVALID, "keyed search: tree %u listed twice", tree_idx[i]);
+            seen[tree_idx[i]] = 1;
+        }
+        SPAI_TRY(upload_noise_keys(e, n, game_id, move_no));
+    }
+    SPAI_TRY(run_search(e, n, num_searches, evals, keyed));
     SPAI_TRY(root_stats(e, n));
     std::vector<Board> rb(Tr.n);
     SPAI_HIP(hipMemcpy(rb.data(), Tr.root_board.p, sizeof(Board) * Tr.n, hipMemcpyDeviceToHost));
@@ -750,6 +848,38 @@ int search(spai_chess *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_sea
         if (policy) dense_policy(rb[tree_idx[i]].side, nch, vis, mv, policy + (size_t)i * kPolicy);
     }
     return SPAI_OK;
+}
+
+int root_noise_draws(spai_chess *e, uint32_t count, const uint64_t *game_id, const uint32_t *move_no,
+                     const uint32_t *n_children, float alpha, float *eta) {
+    if (!count) return SPAI_OK;
+    for (uint32_t i = 0; i < count; ++i)
+        SPAI_CHECK(n_children[i] >= 1 && n_children[i] <= (uint32_t)kMaxChildren, SPAI_ERR_INVALID,
+                   "root noise: n_children[%u] = %u not in [1, %d]", i, n_children[i], kMaxChildren);
+    DevBuf<uint64_t> d_gid;
+    DevBuf<uint32_t> d_move, d_n;
+    DevBuf<float> d_eta;
+    int rc = d_gid.alloc(count);
+    if (rc == SPAI_OK) rc = d_move.alloc(count);
+    if (rc == SPAI_OK) rc = d_n.alloc(count);
+    if (rc == SPAI_OK) rc = d_eta.alloc((size_t)count * kMaxMoves);
+    auto run = [&]() -> int {
+        SPAI_HIP(hipMemcpyAsync(d_gid.p, game_id, 8ull * count, hipMemcpyHostToDevice, e->stream));
+        SPAI_HIP(hipMemcpyAsync(d_move.p, move_no, 4ull * count, hipMemcpyHostToDevice, e->stream));
+        SPAI_HIP(hipMemcpyAsync(d_n.p, n_children, 4ull * count, hipMemcpyHostToDevice, e->stream));
+        k_cnoise_draws<<<blocks_for(count), 64 * kWavesPerBlock, 0, e->stream>>>(count, d_gid.p, d_move.p, d_n.p,
+                                                                                e->cfg.seed, alpha, d_eta.p);
+        SPAI_HIP(hipGetLastError());
+        SPAI_HIP(hipMemcpyAsync(eta, d_eta.p, 4ull * count * kMaxMoves, hipMemcpyDeviceToHost, e->stream));
+        SPAI_HIP(hipStreamSynchronize(e->stream));
+        return SPAI_OK;
+    };
+    if (rc == SPAI_OK) rc = run();
+    d_gid.release();
+    d_move.release();
+    d_n.release();
+    d_eta.release();
+    return rc;
 }
 
 int tree_reset_from_slot(spai_chess *e, uint32_t tree, uint32_t slot) {
@@ -906,6 +1036,9 @@ int selfplay_run(spai_chess *e, uint32_t n_games, uint64_t gid_base, spai_chess_
     std::vector<uint16_t> mvs;
     std::vector<spai_chess_sample> cs;
     std::vector<uint32_t> cvis;
+    const bool noisy = e->noise_eps > 0.0f;   // root noise (spai_chess_set_root_noise)
+    std::vector<uint64_t> ngid;
+    std::vector<uint32_t> nmove;
     // optional per-move trace (diagnostics): SPAI_TRACE_MOVES=<csv path>, lines of
     // move, active games, leaves evaluated, seconds (search + root statistics)
     std::unique_ptr<FILE, int (*)(FILE *)> trace(nullptr, &std::fclose);
@@ -914,8 +1047,17 @@ int selfplay_run(spai_chess *e, uint32_t n_games, uint64_t gid_base, spai_chess_
         const uint32_t na = (uint32_t)act.size();
         const auto tm0 = std::chrono::steady_clock::now();
         SPAI_HIP(hipMemcpyAsync(e->active.p, act.data(), 4 * na, hipMemcpyHostToDevice, e->stream));
+        if (noisy) {   // the move draw's keys: the slot's game id and that game's move number
+            ngid.resize(na);
+            nmove.resize(na);
+            for (uint32_t k = 0; k < na; ++k) {
+                ngid[k] = gid_base + slot_game[act[k]];
+                nmove[k] = slot_move[act[k]];
+            }
+            SPAI_TRY(upload_noise_keys(e, na, ngid.data(), nmove.data()));
+        }
         double ev = 0;
-        SPAI_TRY(run_search(e, na, sims, &ev));
+        SPAI_TRY(run_search(e, na, sims, &ev, noisy));
         SPAI_TRY(root_stats(e, na));
         if (trace)
             std::fprintf(trace.get(), "%llu,%u,%.0f,%.6f\n", (unsigned long long)move_no, na, ev,

@@ -104,12 +104,21 @@ struct Chain {
     spai_chess_net *net = nullptr;      // kind == SPAI_EVAL_NET
     uint32_t sims = 0;
     KernelTimer *timer = nullptr;       // null: nothing is sampled
+    // Dirichlet root noise (dirichlet.h), off unless noise_eps > 0: a match builds its
+    // chains without these fields and so never searches with noise
+    float noise_eps = 0.0f, noise_alpha = 0.0f;
+    uint64_t noise_seed = 0;
+    const uint64_t *noise_gid = nullptr;    // device [n], parallel to active: each tree's game id
+    const uint32_t *noise_move = nullptr;   // device [n], parallel to active: each tree's move number
+    uint32_t *noise_done = nullptr;         // device [n]: the tree's root was noised in this call
 };
 
 TV view(spai_chess *e);
 // the engine's own chain over the first n entries of e->active
 Chain engine_chain(spai_chess *e, uint32_t n, uint32_t sims);
-// enqueue the chain's whole search (compaction, then sims x leaf / forward / expand); n == 0 launches nothing
+// enqueue the chain's whole search (compaction, then sims x leaf / forward / expand); n == 0 launches nothing.
+// With noise_eps > 0 each tree's root children are mixed with a Dirichlet draw once in the call
+// (k_croot_noise): after the compaction where the root has children on entry, else after iteration 0
 int chain_launch(spai_chess *e, const Chain &C);
 // wait for the chain, read its error word and leaf counters (evals = leaves evaluated), account its timer
 int chain_finish(spai_chess *e, const Chain &C, double *evals);

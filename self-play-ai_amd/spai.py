@@ -64,6 +64,7 @@ SYMBOLS = [
     "spai_chess_match_set_one_stream",
     "spai_chess_selfplay_compact", "spai_chess_samples_expand", "spai_chess_learner_train_batch_compact",
     "spai_chess_learner_train_compact", "spai_chess_learner_batch",
+    "spai_chess_set_root_noise", "spai_chess_get_root_noise", "spai_chess_root_noise", "spai_chess_search_keyed",
     # tictactoe (spai_ttt.py)
     "spai_ttt_create", "spai_ttt_destroy", "spai_ttt_games_resize", "spai_ttt_games_write", "spai_ttt_games_read",
     "spai_ttt_legal_mask", "spai_ttt_apply", "spai_ttt_encode", "spai_ttt_mask_invalid", "spai_ttt_net_num_params",

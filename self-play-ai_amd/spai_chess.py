@@ -127,6 +127,10 @@ def lib():
         L.spai_chess_learner_train_batch_compact.argtypes = [vp, u32, vp, vp, vp, u32, vp]
         L.spai_chess_learner_train_compact.argtypes = [vp, u32, vp, vp, vp, u32, u32, u32, u32, u64, vp]
         L.spai_chess_learner_batch.argtypes = [vp, vp, vp, vp, u32]
+        L.spai_chess_set_root_noise.argtypes = [vp, C.c_float, C.c_float]
+        L.spai_chess_get_root_noise.argtypes = [vp, P(C.c_float), P(C.c_float)]
+        L.spai_chess_root_noise.argtypes = [vp, u32, vp, vp, vp, C.c_float, vp]
+        L.spai_chess_search_keyed.argtypes = [vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp]
         _ready = True
     return L
 
@@ -273,7 +277,9 @@ class ChessSamples:
 
 class ChessEngine:
     def __init__(self, num_searches=400, max_trees=1024, eval_kind=EVAL_NET, device=0, c=2.0, temperature=1.25,
-                 seed=0, max_moves=None):
+                 seed=0, max_moves=None, root_noise=None):
+        """root_noise: None (the default: the reference's noise-free search) or (alpha,
+        eps), the Dirichlet root noise of self-play and keyed searches (set_root_noise)"""
         cfg = Config()
         _check(lib().spai_chess_config_default(C.byref(cfg)))
         cfg.c, cfg.num_searches, cfg.temperature = c, num_searches, temperature
@@ -285,6 +291,12 @@ class ChessEngine:
         _check(lib().spai_chess_create(C.byref(cfg), device, C.byref(h)))
         self.h = h
         self.net = None
+        if root_noise is not None:
+            try:
+                self.set_root_noise(*root_noise)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "h", None):
@@ -364,7 +376,37 @@ class ChessEngine:
     def trees_create(self, n):
         _check(lib().spai_chess_trees_create(self.h, n))
 
-    def search(self, trees, num_searches=None):
+    def set_root_noise(self, alpha, eps):
+        """Dirichlet(alpha) root noise of weight eps in self-play and in keyed searches
+        (search(noise_keys=...)); eps = 0 (the default of a new engine) turns it off, and
+        the search is then the reference's.  Plain searches and matches never use it.
+        alpha in [0.01, 100], eps in [0, 1]."""
+        _check(lib().spai_chess_set_root_noise(self.h, float(alpha), float(eps)))
+
+    def root_noise(self):
+        """(alpha, eps) as set; eps 0.0 = off"""
+        a, e = C.c_float(), C.c_float()
+        _check(lib().spai_chess_get_root_noise(self.h, C.byref(a), C.byref(e)))
+        return a.value, e.value
+
+    def root_noise_draws(self, game_ids, move_nos, n_children, alpha=None):
+        """the Dirichlet draws the search makes for these keys, by its own device
+        function: float32 [len][MAX_MOVES], row i zero from n_children[i] on.
+        alpha None: the engine's"""
+        g = np.ascontiguousarray(game_ids, np.uint64).reshape(-1)
+        m = np.ascontiguousarray(move_nos, np.uint32).reshape(-1)
+        k = np.ascontiguousarray(n_children, np.uint32).reshape(-1)
+        if not len(g) == len(m) == len(k):
+            raise ValueError("one game id, move number and child count per draw")
+        a = self.root_noise()[0] if alpha is None else float(alpha)
+        eta = np.zeros((len(g), MAX_MOVES), np.float32)
+        _check(lib().spai_chess_root_noise(self.h, len(g), _p(g), _p(m), _p(k), a, _p(eta)))
+        return eta
+
+    def search(self, trees, num_searches=None, noise_keys=None):
+        """Mcts::search over the listed trees.  noise_keys=(game_ids, move_nos), one pair
+        per tree: the keyed call (spai_chess_search_keyed), which mixes the engine's root
+        noise into each root under that key; without it, or with eps = 0, the plain search"""
         idx = np.ascontiguousarray(trees, np.uint32)
         n = len(idx)
         pol = np.zeros((n, POLICY), np.float32)
@@ -373,7 +415,15 @@ class ChessEngine:
         mv = np.zeros((n, MAX_MOVES), np.uint16)
         nc = np.zeros(n, np.uint32)
         ns = self.cfg.num_searches if num_searches is None else num_searches
-        _check(lib().spai_chess_search(self.h, n, _p(idx), ns, _p(pol), _p(ids), _p(vis), _p(mv), _p(nc)))
+        if noise_keys is None:
+            _check(lib().spai_chess_search(self.h, n, _p(idx), ns, _p(pol), _p(ids), _p(vis), _p(mv), _p(nc)))
+        else:
+            g = np.ascontiguousarray(noise_keys[0], np.uint64).reshape(-1)
+            m = np.ascontiguousarray(noise_keys[1], np.uint32).reshape(-1)
+            if not len(g) == len(m) == n:
+                raise ValueError("noise_keys: one game id and one move number per tree")
+            _check(lib().spai_chess_search_keyed(self.h, n, _p(idx), _p(g), _p(m), ns, _p(pol), _p(ids), _p(vis),
+                                                 _p(mv), _p(nc)))
         return pol, ids, vis, mv, nc
 
     def tree_reset(self, tree, slot):
@@ -681,7 +731,7 @@ class ChessLearner(DeviceLearner):
 def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_games=100, batch_size=32, num_epochs=4,
           num_searches=600, temperature=1.25, c=2.0, blocks=10, seed=0, checkpoint_dir=".", clone_self_play=True,
           params=None, device=0, on_train_set=None, window=None, max_moves=None, compute="f32", refresh="device",
-          on_phase=None, samples="dense"):
+          on_phase=None, samples="dense", root_noise=None):
     """Learner::learn (learner.rs:98-196) for chess, with mcts.rs:46-59's defaults:
     per iteration i, self-play with the current weights on one ChessEngine (the net
     refreshed in place), Model::train on the samples, checkpoint i.safetensors.
@@ -704,6 +754,8 @@ def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_ga
     array; clone_self_play then trains with repeat=num_self_play_iters instead of
     tiling, and on_train_set(i, samples, None, None, game_ids) receives the
     ChessSamples.  Both give the same checkpoints, byte for byte.
+    root_noise: None (the default: the reference's noise-free search) or (alpha, eps),
+    Dirichlet noise at every self-play root (ChessEngine.set_root_noise).
     Returns per-iteration records: samples, loss [total, policy, value] of the last
     step, games, checkpoint."""
     G = num_parallel_self_play_games
@@ -723,7 +775,7 @@ def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_ga
     return learn_loop(
         lambda: ChessEngine(num_searches=num_searches, max_trees=G if window is None else int(window),
                             eval_kind=EVAL_NET, device=device, c=c, temperature=temperature, seed=seed,
-                            max_moves=max_moves),
+                            max_moves=max_moves, root_noise=root_noise),
         lambda eng, P: ChessNet(eng, blocks, P), lambda eng, P: ChessLearner(eng, blocks, P, compute=compute),
         init_params(blocks, seed) if params is None else params, blocks, 256, GAME_CHESS, num_learn_iters,
         num_self_play_iters, G, batch_size, num_epochs, seed, checkpoint_dir, clone_self_play, on_train_set,
