@@ -178,6 +178,37 @@ int spai_tree_reset(spai_engine *eng, uint32_t tree, const spai_c4_state *root);
  * Any output pointer may be NULL. */
 int spai_search(spai_engine *eng, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, float *policy,
                 uint32_t *child_ids, float *child_visits, uint32_t *n_children);
+/* Root exploration noise (AlphaZero's Dirichlet noise; the reference leaves it open,
+ * mcts.rs:204-207), as for chess (spai_chess_set_root_noise).  OPT-IN: an engine is created
+ * with epsilon = 0 and then searches exactly as the reference does, launching nothing more
+ * than before.  With epsilon > 0, every keyed search call (spai_search_keyed, and the
+ * searches of spai_selfplay_run / spai_selfplay_stream) mixes each searched tree's root
+ * priors once, before the call's first selection at that root:
+ *     P_j <- (1 - epsilon) * P_j + epsilon * eta_j,  eta ~ Dirichlet(alpha, ..., alpha)
+ * over the root's children j in stored order (the legal columns, ascending), in float32
+ * with 1 - epsilon rounded once and each product and the sum rounded on their own; no
+ * renormalisation (both vectors sum to 1 up to rounding).  Only the children's prior words
+ * are written; the evaluation cache keeps the net's own priors.  eta is a function of
+ * (cfg.seed, game id, move number, number of children, alpha) alone -- the keys of
+ * self-play's move draw, under a Philox key of its own; for the same values it is the draw
+ * spai_chess_root_noise returns -- so a game does not depend on the window, on how games
+ * are batched or split over game_id_base, on the search's chains and tail mode or on the
+ * evaluation cache.  The mix is stored in the tree: a root searched twice without a move in
+ * between is mixed twice.  spai_search, spai_match_run and spai_pipeline_run NEVER apply
+ * noise, whatever is set here.
+ * epsilon = 0 (default; alpha's default is 0.3): off.  alpha in [0.01, 100], epsilon in
+ * [0, 1], else SPAI_ERR_INVALID (a NaN is out of range) */
+int spai_set_root_noise(spai_engine *eng, float alpha, float epsilon);
+int spai_get_root_noise(spai_engine *eng, float *alpha, float *epsilon);
+/* the draws themselves, by the search's own device function: eta [count][7], entries
+ * >= n_children[i] zero; n_children[i] in [1, 7]; seed = cfg.seed */
+int spai_root_noise(spai_engine *eng, uint32_t count, const uint64_t *game_id, const uint32_t *move_no,
+                    const uint32_t *n_children, float alpha, float *eta);
+/* spai_search with root noise keyed per tree (the engine's alpha / epsilon; epsilon 0 = spai_search);
+ * with epsilon > 0 a tree may be listed once only, else SPAI_ERR_INVALID */
+int spai_search_keyed(spai_engine *eng, uint32_t n, const uint32_t *tree_idx, const uint64_t *game_id,
+                      const uint32_t *move_no, uint32_t num_searches, float *policy, uint32_t *child_ids,
+                      float *child_visits, uint32_t *n_children);
 /* Tree::use_subtree(child) for a child of the root; the new root keeps N and W (quirk Q4) */
 int spai_tree_use_subtree(spai_engine *eng, uint32_t tree, uint32_t child_id);
 /* arena[node].state for the root or a root child; visits / value_sum of that node (may be NULL) */

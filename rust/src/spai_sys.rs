@@ -227,6 +227,14 @@ extern "C" {
     pub fn spai_tree_reset(e: *mut spai_engine, tree: u32, root: *const spai_c4_state) -> c_int;
     pub fn spai_search(e: *mut spai_engine, n: u32, tree_idx: *const u32, num_searches: u32, policy: *mut f32,
                        child_ids: *mut u32, child_visits: *mut f32, n_children: *mut u32) -> c_int;
+    // Dirichlet root noise, opt-in (epsilon 0 = off: the reference's search); keyed searches and self-play only
+    pub fn spai_set_root_noise(e: *mut spai_engine, alpha: f32, epsilon: f32) -> c_int;
+    pub fn spai_get_root_noise(e: *mut spai_engine, alpha: *mut f32, epsilon: *mut f32) -> c_int;
+    pub fn spai_root_noise(e: *mut spai_engine, count: u32, game_id: *const u64, move_no: *const u32,
+                           n_children: *const u32, alpha: f32, eta: *mut f32) -> c_int;
+    pub fn spai_search_keyed(e: *mut spai_engine, n: u32, tree_idx: *const u32, game_id: *const u64,
+                             move_no: *const u32, num_searches: u32, policy: *mut f32, child_ids: *mut u32,
+                             child_visits: *mut f32, n_children: *mut u32) -> c_int;
     pub fn spai_tree_use_subtree(e: *mut spai_engine, tree: u32, child_id: u32) -> c_int;
     pub fn spai_selfplay_run(e: *mut spai_engine, n_games: u32, game_id_base: u64, sink: spai_sample_sink,
                              user: *mut c_void, stats: *mut spai_selfplay_stats) -> c_int;

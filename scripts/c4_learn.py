@@ -109,7 +109,8 @@ def learn(args):
     cfg = dict(num_learn_iters=args.iters, num_self_play_iters=args.self_play_iters,
                num_parallel_self_play_games=args.games, batch_size=args.batch, num_epochs=args.epochs,
                num_searches=args.sims, blocks=args.blocks, seed=args.seed, clone_self_play=not args.distinct)
-    rec, secs, final = _learn_timed(spai, cfg, window=args.window)
+    noise = tuple(args.root_noise) if args.root_noise else None
+    rec, secs, final = _learn_timed(spai, cfg, window=args.window, root_noise=noise)
     for r in rec:
         print(r)
     per_call = args.play_games
@@ -121,7 +122,7 @@ def learn(args):
         out[spec] = c4_match.play(spai, eng, a, b, args.play_games, per_call, 4, args.seed)
         print(f"last checkpoint vs {spec}: {json.dumps(out[spec])}")
     eng.close()
-    return dict(config=cfg, window=args.window, seconds=secs, iterations=rec,
+    return dict(config=cfg, window=args.window, root_noise=noise, seconds=secs, iterations=rec,
                 match=dict(a="last checkpoint", sims=args.play_sims, games=args.play_games, opening_plies=4, vs=out),
                 note="recorded only: one short run, strength is not asserted")
 
@@ -139,6 +140,8 @@ def main():
     ap.add_argument("--self-play-iters", type=int, default=4)
     ap.add_argument("--distinct", action="store_true", help="clone_self_play=False")
     ap.add_argument("--window", type=int, default=None)
+    ap.add_argument("--root-noise", type=float, nargs=2, default=None, metavar=("ALPHA", "EPS"),
+                    help="--learn: Dirichlet root noise in self-play (spai.learn(root_noise=)); the matches never use it")
     ap.add_argument("--sims", type=int, default=100)
     ap.add_argument("--blocks", type=int, default=2)
     ap.add_argument("--batch", type=int, default=32)

@@ -194,6 +194,9 @@ int spai_engine_destroy(spai_engine *e) {
     e->stats.release();
     e->pow_tab.release();
     e->move_out.release();
+    e->noise_done.release();
+    e->noise_gid.release();
+    e->noise_move.release();
     for (uint32_t *&h : e->h_move)
         if (h) (void)hipHostFree(h);
     for (hipEvent_t ev : e->timer.ev) (void)hipEventDestroy(ev);
@@ -364,6 +367,51 @@ int spai_search(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t n
     if (n) SPAI_PTR(tree_idx);
     return search(e, n, tree_idx, num_searches, policy, child_ids, child_visits, n_children, nullptr);
 }
+int spai_set_root_noise(spai_engine *e, float alpha, float epsilon) {
+    ENG_CHECK(e);
+    SPAI_CHECK(alpha >= 0.01f && alpha <= 100.0f, SPAI_ERR_INVALID, "root noise: alpha %g not in [0.01, 100]",
+               (double)alpha);
+    SPAI_CHECK(epsilon >= 0.0f && epsilon <= 1.0f, SPAI_ERR_INVALID, "root noise: epsilon %g not in [0, 1]",
+               (double)epsilon);
+    e->noise_alpha = alpha;
+    e->noise_eps = epsilon;
+    return SPAI_OK;
+}
+
+int spai_get_root_noise(spai_engine *e, float *alpha, float *epsilon) {
+    ENG_CHECK(e);
+    if (alpha) *alpha = e->noise_alpha;
+    if (epsilon) *epsilon = e->noise_eps;
+    return SPAI_OK;
+}
+
+int spai_root_noise(spai_engine *e, uint32_t count, const uint64_t *game_id, const uint32_t *move_no,
+                    const uint32_t *n_children, float alpha, float *eta) {
+    ENG_CHECK(e);
+    SPAI_CHECK(alpha >= 0.01f && alpha <= 100.0f, SPAI_ERR_INVALID, "root noise: alpha %g not in [0.01, 100]",
+               (double)alpha);
+    if (count) {
+        SPAI_PTR(game_id);
+        SPAI_PTR(move_no);
+        SPAI_PTR(n_children);
+        SPAI_PTR(eta);
+    }
+    return root_noise_draws(e, count, game_id, move_no, n_children, alpha, eta);
+}
+
+int spai_search_keyed(spai_engine *e, uint32_t n, const uint32_t *tree_idx, const uint64_t *game_id,
+                      const uint32_t *move_no, uint32_t num_searches, float *policy, uint32_t *child_ids,
+                      float *child_visits, uint32_t *n_children) {
+    ENG_CHECK(e);
+    if (n) {
+        SPAI_PTR(tree_idx);
+        SPAI_PTR(game_id);
+        SPAI_PTR(move_no);
+    }
+    return search(e, n, tree_idx, num_searches, policy, child_ids, child_visits, n_children, nullptr, game_id,
+                  move_no);
+}
+
 int spai_tree_use_subtree(spai_engine *e, uint32_t t, uint32_t child) { ENG_CHECK(e); return tree_use_subtree(e, t, child); }
 int spai_tree_node(spai_engine *e, uint32_t t, uint32_t node, spai_c4_state *st, uint32_t *visits, float *w) {
     ENG_CHECK(e);

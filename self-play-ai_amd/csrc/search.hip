@@ -22,6 +22,10 @@
 // The first iteration starts with k_select alone, the last ends with k_expand.
 // Leaf batches are double-buffered by iteration parity, and every iteration
 // has its own slot counter (zeroed once per search call).
+// Opt-in Dirichlet root noise (spai_set_root_noise; k_root_noise, chains_launch): with
+// epsilon > 0 a keyed search or self-play call mixes every root's priors once, before
+// the first selection at it, for which the call's first iteration runs unfused
+// (k_expand, k_root_noise, k_select); with epsilon 0 nothing of it is enqueued.
 // The host only sees the trees between moves: root visit counts come back once
 // per search call, or the record of a move step that ran on the device.
 #include <algorithm>
@@ -29,6 +33,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "dirichlet.h"
 #include "search_internal.h"
 
 namespace spai {
@@ -561,6 +566,65 @@ __global__ void k_set_left(TreeView T, const uint32_t *__restrict__ active, uint
     if (i < n) T.left[active[i]] = iters;
 }
 
+// Dirichlet root noise (dirichlet.h), once per tree per search call, one wave per active
+// tree: the prior word of every root child becomes (1 - eps) * P + eps * eta, eta drawn
+// under the tree's key (gid[t], move[t]); lanes < n_children write, no other field and no
+// other node is written, no renormalisation.  Launched twice per call.  entry = 1 (after the
+// call's setup, before its first selection): the trees whose root has children are mixed, and
+// done[t] records for every active tree whether it was.  entry = 0 (behind the unfused
+// k_expand of iteration 0, before the first selection at a root it expanded): the trees not
+// mixed yet whose root has children now.  A root that stays without children is never mixed.
+constexpr int kNoiseWaves = 4;   // waves (trees) per workgroup of the two noise kernels
+__global__ __launch_bounds__(64 * kNoiseWaves) void k_root_noise(TreeView T, const uint32_t *__restrict__ active,
+                                                                uint32_t n_active,
+                                                                const uint64_t *__restrict__ gid,
+                                                                const uint32_t *__restrict__ move, uint32_t *done,
+                                                                int entry, uint64_t seed, float alpha,
+                                                                float one_minus_eps, float eps) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t gi = blockIdx.x * kNoiseWaves + (threadIdx.x >> 6);
+    if (gi >= n_active) return;            // (per wave: every lane of a wave that goes on reaches the draw)
+    const uint32_t t = active[gi];
+    if (!entry && done[t]) return;
+    uint4 *nodes = T.nodes + (size_t)t * T.cap;
+    const uint32_t w = nodes[T.root[t]].w;
+    const uint32_t nch = w == kNoChildren ? 0u : w >> 24, first = w & 0xFFFFFFu;
+    if (nch == 0 || nch > (uint32_t)c4::kActions || first + nch > T.cap) {
+        if (entry && lane == 0) done[t] = 0;
+        return;
+    }
+    float eta[4];
+    wave_dirichlet(seed, gid[t], move[t], nch, alpha, lane, eta);
+    if ((uint32_t)lane < nch) {
+        uint32_t *rec = (uint32_t *)(nodes + first + lane);
+        rec[2] = __float_as_uint(dirichlet_mix(__uint_as_float(rec[2]), eta[0], one_minus_eps, eps));
+    }
+    if (lane == 0) done[t] = 1;
+}
+
+// spai_root_noise: the draws themselves, one wave per key; eta [count][7], zero past n[i]
+__global__ __launch_bounds__(64 * kNoiseWaves) void k_noise_draws(uint32_t count, const uint64_t *__restrict__ gid,
+                                                                 const uint32_t *__restrict__ move,
+                                                                 const uint32_t *__restrict__ n, uint64_t seed,
+                                                                 float alpha, float *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t i = blockIdx.x * kNoiseWaves + (threadIdx.x >> 6);
+    if (i >= count) return;
+    float eta[4];
+    wave_dirichlet(seed, gid[i], move[i], n[i], alpha, lane, eta);
+    if (lane < c4::kActions) out[(size_t)i * c4::kActions + lane] = eta[0];
+}
+
+// a keyed search's keys [n], parallel to `active`, into the per-tree key arrays
+__global__ void k_noise_keys(const uint32_t *__restrict__ active, uint32_t n, const uint64_t *__restrict__ gid,
+                             const uint32_t *__restrict__ move, uint64_t *__restrict__ tree_gid,
+                             uint32_t *__restrict__ tree_move) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    tree_gid[active[i]] = gid[i];
+    tree_move[active[i]] = move[i];
+}
+
 __global__ __launch_bounds__(kBlock) void k_eval_stub(BatchView B, uint32_t max_n, int kind) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= max_n || s >= *B.count) return;
@@ -1047,6 +1111,25 @@ static int evaluate(const Chain &c, hipStream_t st, const BatchView &bv, uint32_
     return SPAI_OK;
 }
 
+// k_root_noise over the n trees of act on stream st (entry: see the kernel)
+static int root_noise_launch(spai_engine *e, const RootNoise &N, hipStream_t st, const uint32_t *act, uint32_t n,
+                             int entry) {
+    if (!n) return SPAI_OK;
+    k_root_noise<<<(n + kNoiseWaves - 1) / kNoiseWaves, 64 * kNoiseWaves, 0, st>>>(
+        tree_view(e), act, n, N.gid, N.move, N.done, entry, N.seed, N.alpha, 1.0f - N.eps, N.eps);
+    SPAI_HIP(hipGetLastError());
+    return SPAI_OK;
+}
+
+int root_noise_prepare(spai_engine *e, RootNoise &out, bool &on) {
+    on = e->noise_eps > 0.0f;
+    if (!on) return SPAI_OK;
+    Trees &T = e->trees;
+    if (e->noise_done.n < T.n_trees) SPAI_TRY(e->noise_done.alloc(T.n_trees));
+    out = RootNoise{e->noise_alpha, e->noise_eps, e->cfg.seed, T.slot_gid.p, T.slot_move.p, e->noise_done.p};
+    return SPAI_OK;
+}
+
 // Enqueue one search call of `nchain` chains over `trees`, up to the join on the
 // engine stream.  Per chain: select(0); then per iteration: evaluate(it),
 // expand(it)+select(it+1) fused, and expand alone after the last evaluation.  A
@@ -1055,8 +1138,18 @@ static int evaluate(const Chain &c, hipStream_t st, const BatchView &bv, uint32_
 // sample every stride-th iteration: kind 0 the select-bearing launch (k_select /
 // k_expand_select), 1 the evaluator, 2 the last k_expand.  tail: only the setup,
 // with the counters of the tail passes, which the caller runs.
+//
+// noise (root_noise_launch; null: nothing of this is enqueued): the roots that have
+// children on entry are mixed by one launch over all the call's trees behind the setup,
+// before the fork.  A fresh root gets its children from iteration 0's expansion, and
+// k_expand_select would select iteration 1 at it in the same launch, from priors not
+// mixed yet; so iteration 0 of every chain runs unfused: evaluate(0), k_expand, the mix
+// of the chain's roots still unmixed, k_select into batch 1, and the loop goes on at
+// evaluate(1).  k_expand then k_select is what k_expand_select does per tree; the
+// cache's inserts of iteration 0 only land before iteration 1's lookups, which changes
+// hit counts, never results.
 int chains_launch(spai_engine *e, const uint32_t *trees, const Chain *chains, int nchain, uint32_t grid_cap, bool timed,
-                  bool tail) {
+                  bool tail, const RootNoise *noise) {
     hipStream_t st = e->stream;
     // the call's sequence number, from 1: the stamp of the cache entries it claims and hits
     const uint32_t seq = e->cache.seq = e->cache.seq + 1u ? e->cache.seq + 1u : 1u;
@@ -1083,6 +1176,7 @@ int chains_launch(spai_engine *e, const uint32_t *trees, const Chain *chains, in
     SPAI_HIP(hipMemcpyAsync(e->active.p, trees, (size_t)n * 4, hipMemcpyHostToDevice, st));
     SPAI_HIP(hipMemsetAsync(e->err.p, 0, 4, st));
     SPAI_HIP(hipMemsetAsync(e->trees.evals.p, 0, ((size_t)e->trees.n_trees + 2) * 4, st));
+    if (noise && !tail) SPAI_TRY(root_noise_launch(e, *noise, st, e->active.p, n, 1));   // (tail: behind k_set_left)
     // fork: the chains 1.. that have trees start after the setup on the engine stream
     if (n > chains[0].cnt) SPAI_HIP(hipEventRecord(e->ev_fork, st));
     for (int h = 1; h < nchain; ++h)
@@ -1108,7 +1202,17 @@ int chains_launch(spai_engine *e, const uint32_t *trees, const Chain *chains, in
             if (sample) SPAI_TRY(timer_record(e, 1, it, true, sh, h));
             SPAI_TRY(evaluate(c, sh, bv, grid_cap, std::max(conc, 1)));
             if (sample) SPAI_TRY(timer_record(e, 1, it, false, sh, h));
-            if (it + 1 < c.iters) {
+            if (noise && it == 0) {   // unfused, the fresh roots mixed between the expansion and the selection
+                k_expand<<<g8, kBlock, 0, sh>>>(tv, bv, cache, nh, e->err.p);
+                SPAI_TRY(root_noise_launch(e, *noise, sh, act, nh, 0));
+                if (c.iters > 1) {
+                    const bool s2 = timed && (1 % e->timer.stride == 0);
+                    if (s2) SPAI_TRY(timer_record(e, 0, 1, true, sh, h));
+                    k_select<false><<<g8, kBlock, 0, sh>>>(tv, batch_view(e, h, 1, c.cache.tab), cache, act, nh,
+                                                          e->cfg.c, e->err.p, 0u);
+                    if (s2) SPAI_TRY(timer_record(e, 0, 1, false, sh, h));
+                }
+            } else if (it + 1 < c.iters) {
                 const bool s2 = timed && ((it + 1) % e->timer.stride == 0);
                 if (s2) SPAI_TRY(timer_record(e, 0, it + 1, true, sh, h));
                 k_expand_select<false><<<g8, kBlock, 0, sh>>>(tv, bv, batch_view(e, h, it + 1, c.cache.tab), cache,
@@ -1133,7 +1237,8 @@ int chains_launch(spai_engine *e, const uint32_t *trees, const Chain *chains, in
 // Enqueue one search call over n >= 1 validated trees (mcts.rs:214-285 per tree),
 // up to the join of its chains on the engine stream.  Only tail mode waits (once
 // per chunk of passes, for its stop condition).
-int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, SearchRun &R) {
+int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, SearchRun &R,
+                  const RootNoise *noise) {
     const int kind = (int)e->cfg.eval;
     hipStream_t st = e->stream;
     // evaluation cache: allocated on first use; thinned here, between search calls
@@ -1169,7 +1274,7 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
         const uint32_t off = (uint32_t)((uint64_t)n * h / nchain);
         R.chain[h] = Chain{off, (uint32_t)((uint64_t)n * (h + 1) / nchain) - off, num_searches, kind, e->net, cv};
     }
-    SPAI_TRY(chains_launch(e, tree_idx, R.chain, nchain, pol.grid_cap, true, tail));
+    SPAI_TRY(chains_launch(e, tree_idx, R.chain, nchain, pol.grid_cap, true, tail, noise));
     cv.seq = e->cache.seq;   // (the tail passes below are this call's too)
     R.n_counts = num_searches;   // leaf counters to read back per chain
     if (tail) {
@@ -1183,8 +1288,20 @@ int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t
         const uint32_t g8 = (n + kTreesPerBlock - 1) / kTreesPerBlock;
         const uint32_t *act = e->active.p;
         k_set_left<<<(n + 255) / 256, 256, 0, st>>>(tv, act, n, num_searches);
+        if (noise) SPAI_TRY(root_noise_launch(e, *noise, st, act, n, 1));
         k_select<true><<<g8, kBlock, 0, st>>>(tv, batch_view(e, 0, 0, cv.tab), cv, act, n, e->cfg.c, e->err.p, tail_run);
         uint32_t p = 0, next = 1, more = 0, next_hits = 0;
+        if (noise) {
+            // pass 0 unfused (chains_launch): select<true> runs on through terminal children, so a
+            // fresh root must be mixed before the first selection at it, not after the pass
+            const BatchView bv = batch_view(e, 0, 0, cv.tab);
+            SPAI_TRY(evaluate(R.chain[0], st, bv, 0u, 1));
+            k_expand<<<g8, kBlock, 0, st>>>(tv, bv, cv, n, e->err.p);
+            SPAI_TRY(root_noise_launch(e, *noise, st, act, n, 0));
+            k_select<true><<<g8, kBlock, 0, st>>>(tv, batch_view(e, 0, 1, cv.tab), cv, act, n, e->cfg.c, e->err.p,
+                                                 tail_run);
+            p = 1;
+        }
         for (;;) {
             for (uint32_t q = 0; q < tail_chunk; ++q, ++p) {
                 const BatchView bv = batch_view(e, 0, p, cv.tab);
@@ -1246,7 +1363,8 @@ int search_finish(spai_engine *e, const SearchRun &R, uint32_t num_searches, con
 }
 
 int search(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, float *policy,
-           uint32_t *child_ids, float *child_visits, uint32_t *n_children, double *evals_out) {
+           uint32_t *child_ids, float *child_visits, uint32_t *n_children, double *evals_out,
+           const uint64_t *game_id, const uint32_t *move_no) {
     Trees &T = e->trees;
     SPAI_CHECK(T.n_trees > 0, SPAI_ERR_INVALID, "no trees: call spai_trees_create first");
     SPAI_CHECK(n <= T.n_trees, SPAI_ERR_INVALID, "search over %u trees, %u exist", n, T.n_trees);
@@ -1256,7 +1374,28 @@ int search(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_se
     if (n == 0) return SPAI_OK;
     hipStream_t st = e->stream;
     SearchRun R;
-    SPAI_TRY(search_launch(e, n, tree_idx, num_searches, R));
+    RootNoise noise{};
+    bool keyed = false;
+    if (game_id && move_no) SPAI_TRY(root_noise_prepare(e, noise, keyed));
+    if (keyed) {
+        // a tree listed twice would be mixed twice in one call, by two waves at once
+        std::vector<char> seen(T.n_trees, 0);
+        for (uint32_t i = 0; i < n; ++i) {
+            SPAI_CHECK(!seen[tree_idx[i]], SPAI_ERR_INVALID, "keyed search: tree %u listed twice", tree_idx[i]);
+            seen[tree_idx[i]] = 1;
+        }
+        // the keys go into the per-tree arrays self-play keeps its own in (k_slots_start
+        // resets those at the start of every self-play call)
+        if (e->noise_gid.n < n) SPAI_TRY(e->noise_gid.alloc(T.n_trees));
+        if (e->noise_move.n < n) SPAI_TRY(e->noise_move.alloc(T.n_trees));
+        SPAI_HIP(hipMemcpyAsync(e->active.p, tree_idx, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        SPAI_HIP(hipMemcpyAsync(e->noise_gid.p, game_id, (size_t)n * 8, hipMemcpyHostToDevice, st));
+        SPAI_HIP(hipMemcpyAsync(e->noise_move.p, move_no, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        k_noise_keys<<<(n + 255) / 256, 256, 0, st>>>(e->active.p, n, e->noise_gid.p, e->noise_move.p, T.slot_gid.p,
+                                                     T.slot_move.p);
+        SPAI_HIP(hipGetLastError());
+    }
+    SPAI_TRY(search_launch(e, n, tree_idx, num_searches, R, keyed ? &noise : nullptr));
     const TreeView tv = tree_view(e);
     const int nchain = R.nchain;
     const uint32_t n_counts = R.n_counts;
@@ -1299,6 +1438,39 @@ int search(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_se
         if (policy) normalize_policy(pol, policy + (size_t)i * 7);
     }
     return SPAI_OK;
+}
+
+int root_noise_draws(spai_engine *e, uint32_t count, const uint64_t *game_id, const uint32_t *move_no,
+                     const uint32_t *n_children, float alpha, float *eta) {
+    if (!count) return SPAI_OK;
+    for (uint32_t i = 0; i < count; ++i)
+        SPAI_CHECK(n_children[i] >= 1 && n_children[i] <= (uint32_t)c4::kActions, SPAI_ERR_INVALID,
+                   "root noise: n_children[%u] = %u not in [1, %d]", i, n_children[i], c4::kActions);
+    DevBuf<uint64_t> d_gid;
+    DevBuf<uint32_t> d_move, d_n;
+    DevBuf<float> d_eta;
+    int rc = d_gid.alloc(count);
+    if (rc == SPAI_OK) rc = d_move.alloc(count);
+    if (rc == SPAI_OK) rc = d_n.alloc(count);
+    if (rc == SPAI_OK) rc = d_eta.alloc((size_t)count * c4::kActions);
+    auto run = [&]() -> int {
+        hipStream_t st = e->stream;
+        SPAI_HIP(hipMemcpyAsync(d_gid.p, game_id, 8ull * count, hipMemcpyHostToDevice, st));
+        SPAI_HIP(hipMemcpyAsync(d_move.p, move_no, 4ull * count, hipMemcpyHostToDevice, st));
+        SPAI_HIP(hipMemcpyAsync(d_n.p, n_children, 4ull * count, hipMemcpyHostToDevice, st));
+        k_noise_draws<<<(count + kNoiseWaves - 1) / kNoiseWaves, 64 * kNoiseWaves, 0, st>>>(
+            count, d_gid.p, d_move.p, d_n.p, e->cfg.seed, alpha, d_eta.p);
+        SPAI_HIP(hipGetLastError());
+        SPAI_HIP(hipMemcpyAsync(eta, d_eta.p, 4ull * count * c4::kActions, hipMemcpyDeviceToHost, st));
+        SPAI_HIP(hipStreamSynchronize(st));
+        return SPAI_OK;
+    };
+    if (rc == SPAI_OK) rc = run();
+    d_gid.release();
+    d_move.release();
+    d_n.release();
+    d_eta.release();
+    return rc;
 }
 
 int tree_use_subtree(spai_engine *e, uint32_t t, uint32_t child) {

@@ -159,6 +159,20 @@ struct SearchRun {
 };
 constexpr uint32_t kTailChunk = 4;   // tail mode: passes per host check
 
+// Dirichlet root noise of one search call (dirichlet.h, k_root_noise in search.hip); a
+// launcher given none (null) enqueues nothing for it: spai_search, a match and an engine
+// whose epsilon is 0.  The keys and the flag are per tree, not per entry of `active`.
+struct RootNoise {
+    float alpha, eps;
+    uint64_t seed;
+    const uint64_t *gid;    // device [n_trees]: each tree's game id (self-play: Trees::slot_gid)
+    const uint32_t *move;   // device [n_trees]: each tree's move number (self-play: Trees::slot_move)
+    uint32_t *done;         // device [n_trees]: the tree's root was mixed in this call
+};
+// the engine's noise over the per-tree key arrays, its flag array allocated on first use;
+// on = false when its epsilon is 0 (then `out` is not to be passed on)
+int root_noise_prepare(spai_engine *e, RootNoise &out, bool &on);
+
 TreeView tree_view(spai_engine *e);
 CacheView cache_view(spai_engine *e);   // the engine's cache at its current generation
 inline RootsOut roots_out(spai_engine *e) {
@@ -178,8 +192,9 @@ inline bool cache_nearly_full(const EvalCache &C) { return C.buckets && (uint64_
 void cache_account(spai_engine *e, double served, double forwarded, uint32_t fill);
 int check_device_errors(spai_engine *e, uint32_t err);
 int chains_launch(spai_engine *e, const uint32_t *trees, const Chain *chains, int nchain, uint32_t grid_cap, bool timed,
-                  bool tail);
-int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, SearchRun &R);
+                  bool tail, const RootNoise *noise = nullptr);
+int search_launch(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, SearchRun &R,
+                  const RootNoise *noise = nullptr);
 int search_finish(spai_engine *e, const SearchRun &R, uint32_t num_searches, const uint32_t *ch_counts, uint32_t err,
                   uint32_t max_tree_evals, double served, uint32_t cache_fill);
 int move_buffers(spai_engine *e, size_t n_words);   // selfplay.hip

@@ -142,6 +142,12 @@ int selfplay_run(spai_engine *e, uint32_t n_games, uint64_t gid_base, spai_sampl
     const TreeView tv = tree_view(e);
     const RootsOut ro = roots_out(e);
     SearchRun R;
+    // root noise (spai_set_root_noise): every search is keyed by the move draw's own keys, the
+    // slot's game id and that game's move number, which k_slots_start and k_advance keep per
+    // tree slot on the device; so a game does not depend on the window or on gid_base's split
+    RootNoise noise{};
+    bool noisy = false;
+    SPAI_TRY(root_noise_prepare(e, noise, noisy));
     // every slot starts its first game (id gid_base + slot) at move 0
     k_slots_start<<<(W + 255) / 256, 256, 0, st>>>(tv, ro, T.slot_gid.p, T.slot_move.p, nullptr, W, gid_base);
     SPAI_HIP(hipGetLastError());
@@ -155,7 +161,7 @@ int selfplay_run(spai_engine *e, uint32_t n_games, uint64_t gid_base, spai_sampl
             k_slots_start<<<(nr + 255) / 256, 256, 0, st>>>(tv, ro, T.slot_gid.p, T.slot_move.p, T.refill.p, nr,
                                                            gid_base);
         }
-        SPAI_TRY(search_launch(e, na, a.data(), ns, R));
+        SPAI_TRY(search_launch(e, na, a.data(), ns, R, noisy ? &noise : nullptr));
         ChainCounts cc{{}, {}, R.n_counts};
         for (int h = 0; h < R.nchain; ++h) {
             cc.p[h] = e->batch[h].iter_counts.p;

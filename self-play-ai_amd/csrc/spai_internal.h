@@ -269,6 +269,13 @@ struct spai_engine {
     size_t h_move_n = 0;
     spai::KernelTimer timer;
     spai::EvalCache cache;
+    // Dirichlet root noise (spai_set_root_noise); epsilon 0 = off, and then none of the
+    // buffers below exists.  noise_done [n_trees]: the tree's root was mixed in the current
+    // search call; noise_gid / noise_move [n]: a keyed search's keys on their way into the
+    // per-tree arrays (Trees::slot_gid, slot_move)
+    float noise_alpha = 0.3f, noise_eps = 0.0f;
+    spai::DevBuf<uint32_t> noise_done, noise_move;
+    spai::DevBuf<uint64_t> noise_gid;
 };
 
 namespace spai {
@@ -348,8 +355,13 @@ int pipeline_run(const spai_pipeline_config *cfg, const float *init_params, size
 // search.hip (what it shares with selfplay.hip and match.hip alone: search_internal.h)
 int trees_create(spai_engine *e, uint32_t n);
 int tree_reset(spai_engine *e, uint32_t t, const spai_c4_state *root);
+// game_id / move_no [n] (both or neither): the trees' root-noise keys, read when the engine's epsilon > 0
 int search(spai_engine *e, uint32_t n, const uint32_t *tree_idx, uint32_t num_searches, float *policy,
-           uint32_t *child_ids, float *child_visits, uint32_t *n_children, double *evals_out);
+           uint32_t *child_ids, float *child_visits, uint32_t *n_children, double *evals_out,
+           const uint64_t *game_id = nullptr, const uint32_t *move_no = nullptr);
+// the Dirichlet draws of the given keys by the search's own device function: eta [count][7]
+int root_noise_draws(spai_engine *e, uint32_t count, const uint64_t *game_id, const uint32_t *move_no,
+                     const uint32_t *n_children, float alpha, float *eta);
 int tree_use_subtree(spai_engine *e, uint32_t t, uint32_t child);
 int tree_node(spai_engine *e, uint32_t t, uint32_t node, spai_c4_state *st, uint32_t *visits, float *w);
 int tree_child_stats(spai_engine *e, uint32_t t, uint32_t *child_ids, uint32_t *visits, float *value_sums,

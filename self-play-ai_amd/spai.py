@@ -32,7 +32,8 @@ SYMBOLS = [
     "spai_mask_invalid", "spai_rules_bench", "spai_net_num_params", "spai_net_init_params", "spai_net_create",
     "spai_net_destroy", "spai_net_forward", "spai_predict", "spai_engine_set_net", "spai_net_set_params",
     "spai_net_set_params_from_learner", "spai_trees_create",
-    "spai_tree_reset", "spai_search", "spai_tree_use_subtree", "spai_tree_node", "spai_tree_child_stats", "spai_tree_size",
+    "spai_tree_reset", "spai_search", "spai_set_root_noise", "spai_get_root_noise", "spai_root_noise",
+    "spai_search_keyed", "spai_tree_use_subtree", "spai_tree_node", "spai_tree_child_stats", "spai_tree_size",
     "spai_selfplay_run", "spai_selfplay_stream", "spai_eval_cache_set_capacity", "spai_eval_cache_get_stats",
     "spai_eval_cache_thin",
     "spai_match_config_default", "spai_match_run",
@@ -201,6 +202,10 @@ def lib():
         L.spai_trees_create.argtypes = [vp, u32]
         L.spai_tree_reset.argtypes = [vp, u32, vp]
         L.spai_search.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp]
+        L.spai_set_root_noise.argtypes = [vp, C.c_float, C.c_float]
+        L.spai_get_root_noise.argtypes = [vp, P(C.c_float), P(C.c_float)]
+        L.spai_root_noise.argtypes = [vp, u32, vp, vp, vp, C.c_float, vp]
+        L.spai_search_keyed.argtypes = [vp, u32, vp, vp, vp, u32, vp, vp, vp, vp]
         L.spai_tree_use_subtree.argtypes = [vp, u32, u32]
         L.spai_tree_node.argtypes = [vp, u32, u32, vp, vp, vp]
         L.spai_tree_child_stats.argtypes = [vp, u32, vp, vp, vp, vp, P(u32)]
@@ -353,7 +358,9 @@ class Net:
 
 class Engine:
     def __init__(self, num_searches=800, max_trees=4096, eval_kind=EVAL_NET, device=0, c=2.0, temperature=1.25,
-                 seed=0, max_moves=42, game=GAME_CONNECT4):
+                 seed=0, max_moves=42, game=GAME_CONNECT4, root_noise=None):
+        """root_noise: None (the default: the reference's noise-free search) or (alpha,
+        eps), the Dirichlet root noise of self-play and keyed searches (set_root_noise)"""
         cfg = Config()
         _check(lib().spai_config_default(game, C.byref(cfg)))
         cfg.c, cfg.num_searches, cfg.temperature = c, num_searches, temperature
@@ -363,6 +370,12 @@ class Engine:
         _check(lib().spai_engine_create(game, C.byref(cfg), device, C.byref(h)))
         self.h = h
         self.net = None
+        if root_noise is not None:
+            try:
+                self.set_root_noise(*root_noise)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "h", None):
@@ -443,7 +456,37 @@ class Engine:
             a = states_array([root])
             _check(lib().spai_tree_reset(self.h, t, _p(a)))
 
-    def search(self, tree_idx, num_searches=None):
+    def set_root_noise(self, alpha, eps):
+        """Dirichlet(alpha) root noise of weight eps in self-play and in keyed searches
+        (search(noise_keys=...)); eps = 0 (the default of a new engine) turns it off, and
+        the search is then the reference's.  Plain searches, matches and the pipeline
+        never use it.  alpha in [0.01, 100], eps in [0, 1]."""
+        _check(lib().spai_set_root_noise(self.h, float(alpha), float(eps)))
+
+    def get_root_noise(self):
+        """(alpha, eps) as set; eps 0.0 = off"""
+        a, e = C.c_float(), C.c_float()
+        _check(lib().spai_get_root_noise(self.h, C.byref(a), C.byref(e)))
+        return a.value, e.value
+
+    def root_noise_draws(self, game_ids, move_nos, n_children, alpha=None):
+        """the Dirichlet draws the search makes for these keys, by its own device
+        function: float32 [len][7], row i zero from n_children[i] on.  alpha: the
+        engine's (get_root_noise) unless given.  The seed is the engine's."""
+        g = np.ascontiguousarray(game_ids, np.uint64).reshape(-1)
+        m = np.ascontiguousarray(move_nos, np.uint32).reshape(-1)
+        k = np.ascontiguousarray(n_children, np.uint32).reshape(-1)
+        if not len(g) == len(m) == len(k):
+            raise ValueError("one game id, move number and child count per draw")
+        a = self.get_root_noise()[0] if alpha is None else float(alpha)
+        eta = np.zeros((len(g), 7), np.float32)
+        _check(lib().spai_root_noise(self.h, len(g), _p(g), _p(m), _p(k), a, _p(eta)))
+        return eta
+
+    def search(self, tree_idx, num_searches=None, noise_keys=None):
+        """Mcts::search over the listed trees.  noise_keys=(game_ids, move_nos), one pair
+        per tree: the keyed call (spai_search_keyed), which mixes the engine's root noise
+        into each root under that key; without it, or with eps = 0, the plain search"""
         idx = np.ascontiguousarray(tree_idx, np.uint32)
         n = len(idx)
         ns = self.cfg.num_searches if num_searches is None else num_searches
@@ -451,7 +494,14 @@ class Engine:
         ids = np.zeros((n, 7), np.uint32)
         vis = np.zeros((n, 7), np.float32)
         nc = np.zeros(n, np.uint32)
-        _check(lib().spai_search(self.h, n, _p(idx), ns, _p(pol), _p(ids), _p(vis), _p(nc)))
+        if noise_keys is None:
+            _check(lib().spai_search(self.h, n, _p(idx), ns, _p(pol), _p(ids), _p(vis), _p(nc)))
+        else:
+            g = np.ascontiguousarray(noise_keys[0], np.uint64).reshape(-1)
+            m = np.ascontiguousarray(noise_keys[1], np.uint32).reshape(-1)
+            if not len(g) == len(m) == n:
+                raise ValueError("noise_keys: one game id and one move number per tree")
+            _check(lib().spai_search_keyed(self.h, n, _p(idx), _p(g), _p(m), ns, _p(pol), _p(ids), _p(vis), _p(nc)))
         return pol, ids, vis, nc
 
     def use_subtree(self, t, child_id):
@@ -725,7 +775,8 @@ def load_params(path, blocks, hidden=64, game=GAME_CONNECT4, n=None):
 
 def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_games=100, batch_size=32, num_epochs=4,
           num_searches=600, temperature=1.25, c=2.0, blocks=6, seed=0, checkpoint_dir=".", clone_self_play=True,
-          params=None, device=0, on_train_set=None, window=None, dtype=None, refresh="device", on_phase=None):
+          params=None, device=0, on_train_set=None, window=None, dtype=None, refresh="device", on_phase=None,
+          root_noise=None):
     """Learner::learn (learner.rs:98-196) for Connect4, with mcts.rs:46-59's defaults:
     per iteration i, self-play with the current weights on one Engine (the net
     refreshed in place), Model::train on the samples, checkpoint i.safetensors
@@ -743,6 +794,8 @@ def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_ga
     learner.params()), the same kernel behind a host round trip.  Both give the same
     bits.  on_train_set(i, states, policies, values, game_ids) sees every training
     set; on_phase(i, name, seconds) the host time of each phase (learn_loop).
+    root_noise: None (the default: the reference's noise-free search) or (alpha, eps),
+    Dirichlet noise at every self-play root (Engine.set_root_noise).
     Returns per-iteration records: samples, loss [total, policy, value] of the last
     step, games, checkpoint."""
     if refresh not in ("device", "host"):
@@ -752,7 +805,7 @@ def learn(num_learn_iters=10, num_self_play_iters=500, num_parallel_self_play_ga
     from spai_learn import learn_loop
     return learn_loop(
         lambda: Engine(num_searches=num_searches, max_trees=num_parallel_self_play_games, eval_kind=EVAL_NET,
-                       device=device, c=c, temperature=temperature, seed=seed),
+                       device=device, c=c, temperature=temperature, seed=seed, root_noise=root_noise),
         lambda eng, P: Net(eng, blocks, P, dtype=dtype), lambda eng, P: Learner(eng, blocks, P),
         init_params(blocks, seed=seed) if params is None else params, blocks, 64, GAME_CONNECT4, num_learn_iters,
         num_self_play_iters, num_parallel_self_play_games, batch_size, num_epochs, seed, checkpoint_dir,
